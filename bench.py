@@ -16,7 +16,14 @@ buffers (the library's two work-buffer slots), so two batches are in flight
 and the host's per-call work overlaps the device's, as in a node verifying
 a stream of SyncResponses; the timed region is closed by synchronize.
 
-Rank 0 prints one JSON line.  `value` is the headline above.  Beside it:
+Rank 0 prints one JSON line.  `value` is the headline above and
+`ms_per_step` the wall time of one timed step.  A plain run does no more: it
+sets up, warms up, times the K steps, checks both buffers' bitmasks and
+prints the line.  `--dump-outputs DIR` also writes what the last timed step
+returned (dump_outputs below); the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.  With `--full` the line
+carries beside the headline (`--no-cpu` / `--no-extras` then drop the CPU legs
+/ everything but the roofline):
   * `roofline` — the two verify kernels (k_verify_g + k_verify_q), timed with
     the library's HIP events on the stream they run on, for a batch alone on
     the chip (five synchronous calls after the timed region); see ROOFLINE;
@@ -104,8 +111,13 @@ def parse():
     ap.add_argument("--events", type=int, default=1_000_000, help="events per GPU per step")
     ap.add_argument("--creators", type=int, default=64)
     ap.add_argument("--cpu-seconds", type=float, default=9.0, help="target CPU-baseline sample duration (each leg)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiler passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline calls, every extra leg and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: headline and roofline calls only (profiler passes)")
     ap.add_argument("--inflight", type=int, default=2, choices=(1, 2),
                     help="batches in flight: consecutive steps rotate over this many streams and result buffers")
     ap.add_argument("--dry-run", action="store_true",
@@ -113,7 +125,10 @@ def parse():
     ap.add_argument("--group-logical", type=int, default=0,
                     help="N=1 rehearsal of the N-GPU group leg: bv_group over this many logical shards of GPU 0")
     ap.add_argument("--group-reps", type=int, default=5, help="timed bv_group_verify_batch calls per group leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the headline
+        args.no_cpu = args.no_extras = True
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -192,7 +207,8 @@ def dry_run(args, world: int, rank: int, worker) -> None:
         if not np.array_equal(got[q].numpy().view(np.uint64), expected_words(q, args.events)):
             raise SystemExit(f"rank {rank}: gathered bitmask of rank {q} differs")
     el = time.perf_counter() - t0
-    extras = multi_gpu_legs(args, world, rank, worker, None, 0) if world > 1 or args.group_logical else {}
+    legs = not args.no_extras and (world > 1 or args.group_logical)  # (--full)
+    extras = multi_gpu_legs(args, world, rank, worker, None, 0) if legs else {}
     if rank == 0:
         print(json.dumps(dict({"metric": "ECDSA event verifies/sec", "value": None, "unit": "verifies/s",
                                "n_gpus": world, "steps": 0, "warmup": 0, "ms_per_step": el * 1e3,
@@ -325,6 +341,35 @@ def expected_words(rank: int, n: int, buf: int = 0):
     return np.concatenate([packed, np.zeros(words * 8 - len(packed), np.uint8)]).view(np.uint64)
 
 
+DUMP_HASH_ROWS = 131072
+
+
+def dump_outputs(path: str, res, gathered=None) -> None:
+    """`--dump-outputs DIR`: what the last timed step returned to its caller
+    (the VerifyResult of the buffer it wrote), one float .npy per array, every
+    value exact: `status` (n_items, float32), `accept_bits_u32` (the uint64
+    bitmask words as little-endian 32-bit halves, float64), `msg_hash` (the
+    digest bytes of a fixed seeded sample of DUMP_HASH_ROWS messages, float32;
+    all of them when there are no more) beside `msg_hash_rows` (the sampled
+    message indices, float64) — 21.5 MB at 1M events.  At N > 1 also rank 0's
+    all-gathered bitmask, `gathered_accept_bits_u32`."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n_msgs = len(res.msg_hash)
+    rows = np.arange(n_msgs)
+    if n_msgs > DUMP_HASH_ROWS:
+        rows = np.sort(np.random.default_rng(20240229).choice(n_msgs, DUMP_HASH_ROWS, replace=False))
+    out = {"status": np.asarray(res.status).astype(np.float32),
+           "accept_bits_u32": np.ascontiguousarray(res.accept_bits).view(np.uint32).astype(np.float64),
+           "msg_hash": np.asarray(res.msg_hash)[rows].astype(np.float32),
+           "msg_hash_rows": rows.astype(np.float64)}
+    if gathered is not None:
+        out["gathered_accept_bits_u32"] = gathered.cpu().numpy().view(np.uint32).astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def timed_steps(step, steps: int, warmup: int, world: int, dist, local: int, ver):
     """K steps issued back to back (each a full asynchronous VerifyBatch;
     the library orders a ctx's calls on the device per work-buffer slot, so
@@ -451,8 +496,11 @@ def run(args, world: int, rank: int, local: int, worker) -> None:
         return step
 
     elapsed, tms = timed_steps(step_with(v), args.steps, args.warmup, world, dist, local, v)
+    last = (k[0] - 1) % len(devs)  # the buffer the last timed step wrote
     for j, dev in enumerate(devs):
         res = dev.result()
+        if args.dump_outputs and rank == 0 and j == last:
+            dump_outputs(args.dump_outputs, res, gathered[j] if world > 1 else None)
         if not np.array_equal(res.accept_bits, expected_words(rank, args.events, j)):
             raise SystemExit(f"rank {rank}: accept bitmask (buffer {j}) differs from the expected one")
         if world > 1:  # the all-gathered mask of the buffer's last step: every rank's shard, bit for bit
@@ -465,14 +513,16 @@ def run(args, world: int, rank: int, local: int, worker) -> None:
     # kernels share the CUs with the other batch's, so their HIP-event spans
     # are stretched; the per-launch figures come from a batch alone on the
     # chip (synchronous calls, same workload), right after the timed region.
+    # They are runs of their own: --full only.
     iso = []
-    for _ in range(5):
+    for _ in range(5 if args.full else 0):
         v.verify_device(devs[0], sync=True)
         iso.append(v.timing())
     line = None
     if rank == 0:
         total_items = world * args.events * args.steps
         value = total_items / elapsed
+    if rank == 0 and iso:
         kq_ms, kg_ms = mean(iso, "ms_verify"), mean(iso, "ms_verify_g")
         kv_s = (kq_ms + kg_ms) * 1e-3
         achieved = args.events * MODMUL_PER_ITEM_EXEC * IMUL32_PER_MODMUL / kv_s
@@ -511,6 +561,7 @@ def run(args, world: int, rank: int, local: int, worker) -> None:
             roof["executed_frac"] = i64 * 64 / kv_s / PEAK_IMUL32_PER_S
             roof["valu_issue_frac"] = (i64 * CYC_MAD64 + (ivalu - i64) * CYC_VALU32) / (N_SIMD * 2.4e9 * kv_s)
             roof["pmc_source"] = pmc["tracked_file"]
+    if rank == 0:
         line = {
             "metric": "ECDSA event verifies/sec",
             "value": value,
@@ -535,14 +586,6 @@ def run(args, world: int, rank: int, local: int, worker) -> None:
                 "collective": "RCCL all_gather of accept bitmasks" if world > 1 else None,
                 "batches_in_flight": args.inflight,
             },
-            "breakdown_ms": {  # one batch alone on the chip (5 synchronous calls)
-                "k_sha256": mean(iso, "ms_sha256"),
-                "keyprep_stream": mean(iso, "ms_keyprep"),
-                "k_sinv": mean(iso, "ms_scalar"),
-                "k_verify_g": kg_ms,
-                "k_verify_q": kq_ms,
-                "device_total": mean(iso, "ms_total"),
-            },
             # host time to issue one step (the library's launch work + Python):
             # when it reaches ms_per_step the run is host-bound, not device-bound
             "host_issue_ms_per_step": timed_steps.issue_ms_per_step,
@@ -551,12 +594,21 @@ def run(args, world: int, rank: int, local: int, worker) -> None:
                 "k_verify_g": mean(tms, "ms_verify_g"),
                 "k_verify_q": mean(tms, "ms_verify"),
             },
-            "roofline": roof,
             "bitmask_check": f"exact: {world} x {args.events} events, accept bits all-gathered and equal to the "
                              f"expected mask ({len(corrupted(0, args.events))} seeded r-bit flips per rank and "
                              f"in-flight buffer, a different set per buffer, rejected)",
             "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "default (4)"),
         }
+        if iso:
+            line["breakdown_ms"] = {  # one batch alone on the chip (5 synchronous calls)
+                "k_sha256": mean(iso, "ms_sha256"),
+                "keyprep_stream": mean(iso, "ms_keyprep"),
+                "k_sinv": mean(iso, "ms_scalar"),
+                "k_verify_g": kg_ms,
+                "k_verify_q": kq_ms,
+                "device_total": mean(iso, "ms_total"),
+            }
+            line["roofline"] = roof
     if probe:
         host_entry_rate(v, batch, "after the headline steps")
     if rank == 0 and world == 1 and not args.no_extras:

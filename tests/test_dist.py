@@ -182,7 +182,7 @@ def test_bench_launcher_starts_n_ranks_dry_run():
     two ranks itself (one child torch.distributed.run, rendezvous on
     127.0.0.1); in gloo dry-run mode rank 0 prints ONE line with n_gpus 2
     after the all-gathered bitmasks check out."""
-    p = _bench(["--gpus", "2", "--dry-run", "--events", "5000"])
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--events", "5000"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -202,7 +202,7 @@ def test_bench_group_logical_dry_run():
     """`--group-logical 2` at N = 1 (the one-GPU rehearsal of the group leg):
     the worker is started before any GPU use and released after the
     headline; in dry-run mode it merges two logical shards' words."""
-    p = _bench(["--dry-run", "--group-logical", "2", "--events", "3000"])
+    p = _bench(["--dry-run", "--full", "--group-logical", "2", "--events", "3000"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -273,7 +273,7 @@ def _assert_failed_cleanly(p, events: int):
 def test_bench_fewer_gpus_than_ranks_fails_without_a_line():
     """Ranks that see fewer GPUs than --gpus exit 4 before any work; the
     launcher fails and prints nothing."""
-    p = _bench(["--gpus", "2", "--dry-run", "--events", "5011"], env={"BENCH_DRY_VISIBLE_GPUS": "1"})
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--events", "5011"], env={"BENCH_DRY_VISIBLE_GPUS": "1"})
     _assert_failed_cleanly(p, 5011)
     assert "GPU(s) visible" in p.stderr
 
@@ -281,7 +281,7 @@ def test_bench_fewer_gpus_than_ranks_fails_without_a_line():
 def test_bench_collective_init_failure_fails_without_a_line():
     """The ranks' collective initialisation failing (RCCL at N > 1) ends the
     run non-zero, no line, no child left."""
-    p = _bench(["--gpus", "2", "--dry-run", "--events", "5012"], env={"BENCH_DRY_FAULT": "rccl_init"})
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--events", "5012"], env={"BENCH_DRY_FAULT": "rccl_init"})
     _assert_failed_cleanly(p, 5012)
     assert "RCCL" in p.stderr
 
@@ -290,7 +290,7 @@ def test_bench_rank_crash_fails_without_a_line():
     """Rank 1 dying after the rendezvous (no cleanup): torch.distributed.run
     stops rank 0, rank 0's group worker sees EOF and exits, and the launcher
     exits non-zero without a line."""
-    p = _bench(["--gpus", "2", "--dry-run", "--events", "5013"], env={"BENCH_DRY_FAULT": "rank_crash"})
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--events", "5013"], env={"BENCH_DRY_FAULT": "rank_crash"})
     _assert_failed_cleanly(p, 5013)
 
 
@@ -299,7 +299,7 @@ def test_bench_group_worker_crash_is_recorded_and_reaped():
     process) crashing is an extra leg's failure: the line records it as the
     group leg's error, the headline plumbing stands, and the worker is
     reaped."""
-    p = _bench(["--gpus", "2", "--dry-run", "--events", "5014"], env={"BENCH_DRY_FAULT": "worker_crash"})
+    p = _bench(["--gpus", "2", "--dry-run", "--full", "--events", "5014"], env={"BENCH_DRY_FAULT": "worker_crash"})
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
