@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import subprocess
 
 import numpy as np
 
@@ -24,13 +25,22 @@ class ShimWire(ctypes.Structure):
 _lib = None
 
 
+def lib_path() -> str:
+    """LIB_PATH, made first when it is not there (as coracle.lib() does for
+    the oracle): __graft_entry__.build() leaves it in place, but a tests/
+    tree put over a built checkout has only the sources."""
+    if not os.path.exists(LIB_PATH):
+        subprocess.run(["make", "-s", "-C", HERE], check=True)
+    return LIB_PATH
+
+
 def lib():
     global _lib
     if _lib is None:
         from babble_amd import native
 
         native.lib()  # libbabbleverify.so first (torch's HIP runtime), so the harness binds to the same copy
-        L = ctypes.CDLL(LIB_PATH)
+        L = ctypes.CDLL(lib_path())
         L.shim_open.argtypes = [ctypes.c_int, ctypes.c_uint32]
         L.shim_close.restype = None
         L.shim_last_error.restype = ctypes.c_char_p

@@ -18,13 +18,14 @@ from tests.cabi import harness
 
 
 def test_harness_exports():
-    out = subprocess.run(["nm", "-D", "--defined-only", harness.LIB_PATH], capture_output=True, text=True,
+    lib = harness.lib_path()  # made here when build() has not left it in this tests/ tree
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True,
                          check=True).stdout
     names = {line.split()[-1] for line in out.splitlines() if " T " in line}
     assert {"shim_open", "shim_close", "shim_set_peers", "shim_sync", "shim_verify_event",
             "shim_encode_signatures"} <= names
     # it calls the library only through the C ABI (no HIP symbol of its own)
-    und = subprocess.run(["nm", "-D", "--undefined-only", harness.LIB_PATH], capture_output=True, text=True,
+    und = subprocess.run(["nm", "-D", "--undefined-only", lib], capture_output=True, text=True,
                          check=True).stdout
     assert not [x for x in und.split() if x.startswith("hip")]
     assert "bv_arena_reserve" in und and "bv_verify_events" in und and "bv_kc_register" in und

@@ -146,7 +146,9 @@ def test_c4_adversarial_1m(verifier):
     creators), the per-million corruption and malformed-key mix; every
     digest, status and accept bit equal to the C oracle's.  At 15.6k items
     per key this runs the signed-digit K12 tables (incl. digits 2^11 and the
-    top-window carry at scale)."""
+    top-window carry at scale; random scalars do not reach the same digits
+    of the 26-bit generator windows or the 22-bit KC windows: those are
+    forced by tests/test_gpu_edge_vectors.py)."""
     b = synth.adversarial(1_000_000, seed=4)
     res = check_against_oracle(verifier, b)
     assert verifier.timing()["key_path"] == 12
