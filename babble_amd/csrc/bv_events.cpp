@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "bv_internal.h"
+#include "evjson.h"
 
 #define HIPCHK(expr, code, what)                               \
   do {                                                         \
@@ -101,18 +102,23 @@ struct SigOut {
   uint8_t *r = nullptr, *s = nullptr, *pre = nullptr;
 };
 int sig_decode_on_device(bv_ctx *ctx, uint64_t n, const uint64_t *d_off, const uint8_t *d_text, hipEvent_t text_ready,
-                         SigOut *out) {
+                         SigOut *out, uint64_t text_base = 0) {
   const size_t rs = align256(n * 32);
   HIPCHK(ctx->d_sig.ensure(2 * rs + align256(n)), BV_E_OOM, "alloc decoded signatures");
   uint8_t *base = ctx->d_sig.as<uint8_t>();
   out->r = base, out->s = base + rs, out->pre = base + 2 * rs;
   HIPCHK(hipStreamWaitEvent(ctx->sstream, text_ready, 0), BV_E_LAUNCH, "join signature text");
-  HIPCHK(bvk::sig_decode(ctx->sstream, n, d_off, d_text, out->r, out->s, out->pre), BV_E_LAUNCH, "k_sig_decode");
+  // (a shard's text: the offsets are the whole batch's, the text starts at byte text_base)
+  HIPCHK(text_base ? bvk::sig_decode_rb(ctx->sstream, n, d_off, d_text, text_base, out->r, out->s, out->pre)
+                   : bvk::sig_decode(ctx->sstream, n, d_off, d_text, out->r, out->s, out->pre),
+         BV_E_LAUNCH, "k_sig_decode");
   HIPCHK(hipEventRecord(ctx->S().ev[E_SDEC], ctx->sstream), BV_E_LAUNCH, "event");
   return BV_OK;
 }
 
 }  // namespace
+
+int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb) { return validate(ctx, eb); }
 
 static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *res);
 
@@ -292,11 +298,73 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
     return verify_events_dag_host(ctx, eb, res, order, level_off, call);
   }
 
+  // bulk: the whole batch as one shard with zero bases
+  const bv_ev_shard whole{0, n, 0, eb->parent_hashes ? eb->n_parent_hashes : 0};
+  rc = bv_events_launch(ctx, eb, whole, res, &call);
+  if (rc != BV_OK) return rc;
+  rc = bv_mark_done(ctx, st);
+  if (rc != BV_OK) return rc;
+  return bv_events_finish(ctx, n, res, &call, true);
+}
+
+int bv_events_finish(bv_ctx *ctx, uint64_t n_events, bv_result *res, bv_host_call *call, bool bits_out) {
+  bv_batch sizes = {};
+  sizes.n_msgs = n_events;
+  sizes.n_items = n_events;
+  return bv_host_finish(ctx, &sizes, res, call, bits_out);
+}
+
+// The bulk path over events [sh.a, sh.z) of a validated batch without in-batch
+// parents: everything up to the call's last enqueued command (the caller
+// records the end with bv_mark_done and collects with bv_events_finish).
+// bv_verify_events passes the whole batch; bv_group_verify_events one shard
+// per device slot.  The shard's slices are staged from where they lie in the
+// caller's arrays, and the values in them stay the whole batch's: the device
+// subtracts the bases (evjson.h EvjBases) instead of the host rewriting up to
+// 56 B per event.  With every base zero the un-based kernels run.
+int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard &sh, const bv_result *res,
+                     bv_host_call *call_p) {
+  bv_host_call &call = *call_p;
+  int rc = BV_OK;
+  hipStream_t st = ctx->stream;
+  ctx->timing = bv_timing{};
+  ctx->last = st;
+  const uint64_t n = sh.z - sh.a;  // the shard's events: e below is shard-local
+  if (n == 0) return BV_OK;
+  EvjBases bs = {};
+  bs.ev = sh.a;
+  bs.tx = whole->tx_start[sh.a];
+  bs.txb = whole->tx_start[whole->n_events] ? whole->tx_off[bs.tx] : 0;
+  bs.itx = whole->itx_off ? whole->itx_off[sh.a] : 0;
+  bs.bsig = whole->bsig_off ? whole->bsig_off[sh.a] : 0;
+  bs.ph = sh.hash_lo;
+  const uint64_t sig_base = whole->sig_text ? whole->sig_off[sh.a] : 0;
+  const bool rebased = bs.ev || bs.tx || bs.txb || bs.itx || bs.bsig || bs.ph;
+  // the shard's view of the caller's arrays (host pointers to its first elements)
+  bv_event_batch view = *whole;
+  {
+    auto adv = [](auto *&p, uint64_t k) {
+      if (p) p += k;
+    };
+    view.n_events = n;
+    adv(view.creator, sh.a), adv(view.index, sh.a), adv(view.timestamp, sh.a);
+    adv(view.parent_kind, 2 * sh.a), adv(view.parent_ref, 2 * sh.a);
+    view.n_parent_hashes = sh.hash_hi - sh.hash_lo;
+    adv(view.parent_hashes, 32 * sh.hash_lo);
+    adv(view.tx_start, sh.a), adv(view.tx_off, bs.tx), adv(view.tx_bytes, bs.txb);
+    adv(view.tx_list_nil, sh.a), adv(view.tx_nil, bs.tx);
+    adv(view.itx_off, sh.a), adv(view.itx_json, bs.itx), adv(view.bsig_off, sh.a), adv(view.bsig_json, bs.bsig);
+    adv(view.r_be, 32 * sh.a), adv(view.s_be, 32 * sh.a), adv(view.pre, sh.a);
+    adv(view.sig_off, sh.a), adv(view.sig_text, sig_base);
+  }
+  const bv_event_batch *eb = &view;
+
   // staging layout (pinned host and HBM): the compact wire arrays
-  const uint64_t n_tx = eb->tx_start[n];
-  const uint64_t tx_len = n_tx ? eb->tx_off[n_tx] : 0;
+  const uint64_t n_tx = eb->tx_start[n] - bs.tx;
+  const uint64_t tx_len = n_tx ? eb->tx_off[n_tx] - bs.txb : 0;
   const uint64_t key_len = eb->key_off[eb->n_keys];
-  const uint64_t itx_len = eb->itx_off ? eb->itx_off[n] : 0, bsig_len = eb->bsig_off ? eb->bsig_off[n] : 0;
+  const uint64_t itx_len = eb->itx_off ? eb->itx_off[n] - bs.itx : 0,
+                 bsig_len = eb->bsig_off ? eb->bsig_off[n] - bs.bsig : 0;
   // How a segment splits over an event chunk [e0, e1): ALL = whole, in the
   // first part; EV = `unit` bytes per event; EV1 = an n + 1 offset array
   // (elements e0 ..= e1); TX / TX1 = the same per transaction of the chunk's
@@ -328,7 +396,7 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   // s and pre, or the signature text (decoded on the device into r, s, pre)
   const bool text = eb->sig_text != nullptr;
   const size_t o_s = text ? add(eb->sig_off, (n + 1) * 8, ALL) : add(eb->s_be, n * 32, ALL);
-  const size_t o_pre = text ? add(eb->sig_text, eb->sig_off[n], ALL) : add(eb->pre, eb->pre ? n : 0, ALL);
+  const size_t o_pre = text ? add(eb->sig_text, eb->sig_off[n] - sig_base, ALL) : add(eb->pre, eb->pre ? n : 0, ALL);
   const size_t s_end = total;
   // key part first (ctx->qfirst): r and the creators cross before the
   // chunks, so every item's k1 Q + k2 phi(Q) is summed under the transfer
@@ -355,16 +423,22 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   const size_t o_bo = add(eb->bsig_off, eb->bsig_off ? (n + 1) * 8 : 0, EV1, 8);
   const size_t o_bj = add(eb->bsig_json, bsig_len, BSIG);
   auto seg_range = [&](const Seg &g, uint64_t e0, uint64_t e1, size_t *lo, size_t *hi) {
-    const uint64_t t0 = eb->tx_start[e0], t1 = eb->tx_start[e1];
+    const uint64_t t0 = eb->tx_start[e0] - bs.tx, t1 = eb->tx_start[e1] - bs.tx;
     switch (g.kind) {
       case ALL: *lo = 0; *hi = g.n; break;
       case EV: *lo = e0 * g.unit; *hi = e1 * g.unit; break;
       case EV1: *lo = e0 * g.unit; *hi = (e1 + 1) * g.unit; break;
       case TX: *lo = t0 * g.unit; *hi = t1 * g.unit; break;
       case TX1: *lo = t0 * g.unit; *hi = (t1 + 1) * g.unit; break;
-      case TXB: *lo = n_tx ? eb->tx_off[t0] : 0; *hi = n_tx ? eb->tx_off[t1] : 0; break;
-      case ITX: *lo = eb->itx_off ? eb->itx_off[e0] : 0; *hi = eb->itx_off ? eb->itx_off[e1] : 0; break;
-      case BSIG: *lo = eb->bsig_off ? eb->bsig_off[e0] : 0; *hi = eb->bsig_off ? eb->bsig_off[e1] : 0; break;
+      case TXB: *lo = n_tx ? eb->tx_off[t0] - bs.txb : 0; *hi = n_tx ? eb->tx_off[t1] - bs.txb : 0; break;
+      case ITX:
+        *lo = eb->itx_off ? eb->itx_off[e0] - bs.itx : 0;
+        *hi = eb->itx_off ? eb->itx_off[e1] - bs.itx : 0;
+        break;
+      case BSIG:
+        *lo = eb->bsig_off ? eb->bsig_off[e0] - bs.bsig : 0;
+        *hi = eb->bsig_off ? eb->bsig_off[e1] - bs.bsig : 0;
+        break;
     }
     *hi = std::min(*hi, g.n);
     *lo = std::min(*lo, *hi);
@@ -500,7 +574,7 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   if (ctx->flags & BV_F_KEY_CACHE) {
     HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_KREADY], 0), BV_E_LAUNCH, "join");
     bv_kc_items items;
-    items.n_items = eb->n_events;
+    items.n_items = n;  // the shard's creators
     items.h_item_key = eb->creator;
     rc = bv_kc_prepare(ctx, eb->n_keys, eb->key_bytes, eb->key_off, d.key_bytes, d.key_off, st, &kc, false, &items);
     if (rc != BV_OK) return rc;
@@ -510,7 +584,8 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   HIPCHK(hipEventRecord(ctx->S().ev[E_SREADY], cs), BV_E_LAUNCH, "event");
   if (text) {  // r, s, pre from the text, ahead of s^-1; the verify stream reads them
     SigOut so;
-    rc = sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so);
+    rc = sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so,
+                              sig_base);
     if (rc != BV_OK) return rc;
     vb.r_be = d.r_be = so.r, vb.s_be = d.s_be = so.s, vb.pre = d.pre = so.pre;
     HIPCHK(hipStreamWaitEvent(vst, ctx->S().ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");
@@ -571,7 +646,9 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
     hipEvent_t landed = ctx->chunk_ev[c % ctx->chunk_ev.size()];
     HIPCHK(hipEventRecord(landed, cs), BV_E_LAUNCH, "event");
     HIPCHK(hipStreamWaitEvent(st, landed, 0), BV_E_LAUNCH, "join chunk");
-    HIPCHK(bvk::ev_body_hash(st, d, e0, e1, dig), BV_E_LAUNCH, "k_ev_body_hash");
+    HIPCHK(rebased ? bvk::ev_body_hash_rb(st, d, sh.a + e0, sh.a + e1, bs, dig)
+                   : bvk::ev_body_hash(st, d, e0, e1, dig),
+           BV_E_LAUNCH, "k_ev_body_hash");
     HIPCHK(hipEventRecord(ctx->S().ev[E_HASHED], st), BV_E_LAUNCH, "event");  // the last chunk's record is used
     hipEvent_t hashed = ctx->chunk_ev[(c + 32) % ctx->chunk_ev.size()];  // waited on before chunk c+2's record
     HIPCHK(hipEventRecord(hashed, st), BV_E_LAUNCH, "event");
@@ -617,10 +694,5 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   if (d2h == 2) HIPCHK(hipEventRecord(ctx->S().ev[E_CSDONE], cs), BV_E_LAUNCH, "event");
   HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_CSDONE], 0), BV_E_LAUNCH, "join");  // digests out before ev_done
   HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_STAGED], 0), BV_E_LAUNCH, "join");  // staging free after ev_done
-  rc = bv_mark_done(ctx, st);
-  if (rc != BV_OK) return rc;
-  bv_batch sizes = {};
-  sizes.n_msgs = n;
-  sizes.n_items = n;
-  return bv_host_finish(ctx, &sizes, res, &call, true);
+  return BV_OK;
 }

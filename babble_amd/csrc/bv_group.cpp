@@ -22,6 +22,10 @@
 // concurrent per-shard staging threads, the shifted merge — is the
 // multi-device code path, so it runs on hardware with one GPU
 // (tests/test_gpu_cache_group.py::test_group_logical_shards).
+//
+// Two entries share the gather tail (gather_and_finish): bv_group_verify_batch
+// (serialized bodies, above) and bv_group_verify_events (wire fields, sharded
+// by event index; below).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -187,6 +191,9 @@ extern "C" int bv_group_get_timing(const bv_group *g, int i, bv_timing *out) {
 }
 
 static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPlan &p);
+static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items);
+static int gather_and_finish(bv_group *g, uint64_t words, std::vector<uint64_t> &gathered,
+                             const std::function<int(int, bv_ctx *)> &finish);
 
 extern "C" int bv_group_verify_batch(bv_group *g, const bv_batch *b, bv_result *res) {
   if (!g || !b || !res) return BV_E_ARGS;
@@ -278,20 +285,66 @@ static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPla
       rcs[d] = bv_host_launch(c, &sb[d], &calls[d], &sr);
       if (rcs[d] != BV_OK) return;
       // the shard's bits, zero-padded to `words`, as the all-gather send buffer
-      if (g->send[d].ensure(words * 8) != hipSuccess || g->recv[d].ensure(words * 8 * D) != hipSuccess) {
-        rcs[d] = BV_E_OOM;
-        return;
-      }
-      const uint64_t sw = (sb[d].n_items + 63) / 64;
-      if (hipMemsetAsync(g->send[d].p, 0, words * 8, c->stream) != hipSuccess ||
-          (sw && hipMemcpyAsync(g->send[d].p, c->S().bits.p, sw * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
-          hipEventRecord(g->sent[d], c->stream) != hipSuccess)
-        rcs[d] = BV_E_LAUNCH;
+      rcs[d] = stage_shard_bits(g, d, words, sb[d].n_items);
     });
   for (auto &t : th) t.join();
   for (int d = 0; d < D; d++)
     if (rcs[d] != BV_OK) return gfail(g, rcs[d], "device " + std::to_string(g->devices[d]) + ": " + g->ctx[d]->err);
 
+  // per-device results (digests of its message range, statuses of its shard)
+  std::vector<uint64_t> gathered;
+  rc = gather_and_finish(g, words, gathered, [&](int d, bv_ctx *c) {
+    bv_result sr = {};
+    sr.msg_hash = res->msg_hash ? res->msg_hash + 32 * p.mlo[d] : nullptr;
+    sr.status = st_out ? st_out + bounds[d] : nullptr;
+    return bv_host_finish(c, &sb[d], &sr, &calls[d], false);
+  });
+  if (rc != BV_OK) return rc;
+  if (!res->accept_bits && !p.permuted) return BV_OK;
+  // merge the shard-local words into the bitmask (message order), then back
+  // to the caller's item order when the items were permuted
+  const uint64_t n = b->n_items, W = (n + 63) / 64;
+  uint64_t *merged = res->accept_bits;
+  if (p.permuted) {
+    p.s_bits.assign(std::max<uint64_t>(W, 1), 0);
+    merged = p.s_bits.data();
+  }
+  if (merged && bv_merge_shard_bits(gathered.data(), words, D, bounds.data(), merged) != BV_OK)
+    return gfail(g, BV_E_ARGS, "merge shard bits");
+  if (p.permuted) {
+    if (res->status)
+      for (uint64_t j = 0; j < n; j++) res->status[p.perm[j]] = p.s_status[j];
+    if (res->accept_bits) {
+      memset(res->accept_bits, 0, W * 8);
+      for (uint64_t j = 0; j < n; j++)
+        if (merged[j >> 6] >> (j & 63) & 1) res->accept_bits[p.perm[j] >> 6] |= 1ull << (p.perm[j] & 63);
+    }
+  }
+  return BV_OK;
+}
+
+// A shard's accept bits (`n_items` of them, in its ctx's slot; none for an
+// empty shard), zero-padded to `words`, as the gather's send buffer on its
+// ctx's stream.  Called with the ctx locked and its device current.
+static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items) {
+  bv_ctx *c = g->ctx[d];
+  const int D = (int)g->ctx.size();
+  if (g->send[d].ensure(words * 8) != hipSuccess || g->recv[d].ensure(words * 8 * D) != hipSuccess) return BV_E_OOM;
+  const uint64_t sw = (n_items + 63) / 64;
+  if (hipMemsetAsync(g->send[d].p, 0, words * 8, c->stream) != hipSuccess ||
+      (sw && hipMemcpyAsync(g->send[d].p, c->S().bits.p, sw * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
+      hipEventRecord(g->sent[d], c->stream) != hipSuccess)
+    return BV_E_LAUNCH;
+  return BV_OK;
+}
+
+// The tail both group entries share, after every shard was launched and its
+// send buffer staged: the gather of the shard bitmasks (`words` each) into
+// `gathered` on the host, then each device's results through `finish`, called
+// with that ctx locked, its device current and the call's end recorded.
+static int gather_and_finish(bv_group *g, uint64_t words, std::vector<uint64_t> &gathered,
+                             const std::function<int(int, bv_ctx *)> &finish) {
+  const int D = (int)g->ctx.size();
   if (g->logical) {
     // logical shards of one device: the gather is D copies into shard 0's
     // buffer on shard 0's stream, each ordered after that shard's send
@@ -312,43 +365,130 @@ static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPla
     const int r2 = g_rccl.group_end();
     if (r != 0 || r2 != 0) return gfail(g, BV_E_COMM, std::string("ncclAllGather: ") + g_rccl.errstr(r ? r : r2));
   }
-  std::vector<uint64_t> gathered(words * D);
+  gathered.assign(words * D, 0);
   (void)hipSetDevice(g->devices[0]);
   if (hipMemcpyAsync(gathered.data(), g->recv[0].p, words * 8 * D, hipMemcpyDeviceToHost, g->ctx[0]->stream) !=
       hipSuccess)
     return gfail(g, BV_E_LAUNCH, "d2h gathered bits");
-
-  // per-device results (digests of its message range, statuses of its shard)
   for (int d = 0; d < D; d++) {
     bv_ctx *c = g->ctx[d];
     std::lock_guard<std::mutex> clk(c->mu);
     (void)hipSetDevice(c->device);
     if (bv_mark_done(c, c->stream) != BV_OK) return gfail(g, BV_E_LAUNCH, "event");
-    bv_result sr = {};
-    sr.msg_hash = res->msg_hash ? res->msg_hash + 32 * p.mlo[d] : nullptr;
-    sr.status = st_out ? st_out + bounds[d] : nullptr;
-    rc = bv_host_finish(c, &sb[d], &sr, &calls[d], false);
+    const int rc = finish(d, c);
     if (rc != BV_OK) return gfail(g, rc, c->err);
   }
-  if (!res->accept_bits && !p.permuted) return BV_OK;
-  // merge the shard-local words into the bitmask (message order), then back
-  // to the caller's item order when the items were permuted
-  const uint64_t n = b->n_items, W = (n + 63) / 64;
-  uint64_t *merged = res->accept_bits;
-  if (p.permuted) {
-    p.s_bits.assign(std::max<uint64_t>(W, 1), 0);
-    merged = p.s_bits.data();
+  return BV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// bv_group_verify_events: the wire-field entry (bv_verify_events) sharded by
+// event index.  Bulk batches are cut by bv_plan_event_shards; every slot
+// stages its shard's slices of the caller's arrays as they are and the device
+// subtracts the shard's bases (bv_events_launch, evjson.h EvjBases).  A batch
+// with in-batch parents (a SyncResponse DAG) is one bv_verify_events call on
+// slot 0.
+// ---------------------------------------------------------------------------
+static int group_verify_events(bv_group *g, const bv_event_batch *eb, bv_result *res) {
+  const int D = (int)g->ctx.size();
+  const uint64_t n = eb->n_events;
+  if (n > (1ull << 32)) return gfail(g, BV_E_ARGS, "more than 2^32 events in one group call");
+  bv_ctx *c0 = g->ctx[0];
+  if (n && eb->parent_kind && memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n)) {
+    const int rc = bv_verify_events(c0, eb, res);  // (validates the batch itself)
+    return rc == BV_OK ? rc : gfail(g, rc, c0->err);
   }
-  if (merged && bv_merge_shard_bits(gathered.data(), words, D, bounds.data(), merged) != BV_OK)
+  {
+    std::lock_guard<std::mutex> clk(c0->mu);
+    const int rc = bv_validate_events(c0, eb);
+    if (rc != BV_OK) return gfail(g, rc, c0->err);
+  }
+  if (n == 0) return BV_OK;
+  // the plan of bv_plan_event_shards: the bounds here, each shard's hash
+  // range in its own thread below (a pass over its parents, in pieces on its
+  // ctx's pool: 1M events ~0.2 ms instead of ~1.3 on one core)
+  std::vector<uint64_t> bounds(D + 1);
+  plan_event_bounds(n, D, false, bounds.data());
+  uint64_t words = 1;
+  for (int d = 0; d < D; d++) words = std::max<uint64_t>(words, (bounds[d + 1] - bounds[d] + 63) / 64);
+
+  // stage, build, hash and verify every shard concurrently (one host thread
+  // per slot); digests and statuses go straight to the shard's part of the
+  // caller's buffers
+  auto shard_res = [&](int d) {
+    bv_result sr = {};
+    sr.msg_hash = res->msg_hash ? res->msg_hash + 32 * bounds[d] : nullptr;
+    sr.status = res->status ? res->status + bounds[d] : nullptr;
+    return sr;
+  };
+  std::vector<bv_host_call> calls(D);
+  std::vector<int> rcs(D, BV_OK);
+  std::vector<std::thread> th;
+  for (int d = 0; d < D; d++)
+    th.emplace_back([&, d]() {
+      bv_ctx *c = g->ctx[d];
+      std::lock_guard<std::mutex> clk(c->mu);
+      if (hipSetDevice(c->device) != hipSuccess) {
+        rcs[d] = BV_E_NODEVICE;
+        return;
+      }
+      calls[d].t0 = std::chrono::steady_clock::now();
+      bv_ev_shard sh{bounds[d], bounds[d + 1], UINT64_MAX, 0};
+      std::mutex rmu;
+      c->pool->parallel_for(sh.z - sh.a, 1 << 16, [&](uint64_t p0, uint64_t p1) {
+        uint64_t lo = 0, hi = 0;
+        (void)event_hash_range(eb, sh.a + p0, sh.a + p1, &lo, &hi);  // (the batch is validated)
+        std::lock_guard<std::mutex> lk(rmu);
+        if (hi) sh.hash_lo = std::min(sh.hash_lo, lo), sh.hash_hi = std::max(sh.hash_hi, hi);
+        return true;
+      });
+      if (!sh.hash_hi) sh.hash_lo = 0;
+      const bv_result sr = shard_res(d);
+      rcs[d] = bv_events_launch(c, eb, sh, &sr, &calls[d]);
+      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.z - sh.a);
+    });
+  for (auto &t : th) t.join();
+  for (int d = 0; d < D; d++)
+    if (rcs[d] != BV_OK) return gfail(g, rcs[d], "device " + std::to_string(g->devices[d]) + ": " + g->ctx[d]->err);
+
+  std::vector<uint64_t> gathered;
+  const int rc = gather_and_finish(g, words, gathered, [&](int d, bv_ctx *c) {
+    if (bounds[d + 1] == bounds[d]) return (int)BV_OK;  // an empty shard launched nothing
+    bv_result sr = shard_res(d);
+    return bv_events_finish(c, bounds[d + 1] - bounds[d], &sr, &calls[d], false);
+  });
+  if (rc != BV_OK) return rc;
+  if (res->accept_bits && bv_merge_shard_bits(gathered.data(), words, D, bounds.data(), res->accept_bits) != BV_OK)
     return gfail(g, BV_E_ARGS, "merge shard bits");
-  if (p.permuted) {
-    if (res->status)
-      for (uint64_t j = 0; j < n; j++) res->status[p.perm[j]] = p.s_status[j];
-    if (res->accept_bits) {
-      memset(res->accept_bits, 0, W * 8);
-      for (uint64_t j = 0; j < n; j++)
-        if (merged[j >> 6] >> (j & 63) & 1) res->accept_bits[p.perm[j] >> 6] |= 1ull << (p.perm[j] & 63);
-    }
+  return BV_OK;
+}
+
+// nothing of a failed group call stays in flight on any slot
+static void drain_all(bv_group *g, int rc) {
+  for (bv_ctx *c : g->ctx) {
+    std::lock_guard<std::mutex> clk(c->mu);
+    (void)hipSetDevice(c->device);
+    (void)bv_drain(c, c->stream, rc);
+  }
+}
+
+extern "C" int bv_group_verify_events(bv_group *g, const bv_event_batch *eb, bv_result *res) {
+  if (!g || !eb || !res) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const int rc = group_verify_events(g, eb, res);
+  if (rc != BV_OK) drain_all(g, rc);
+  return rc;
+}
+
+extern "C" int bv_group_kc_register(bv_group *g, uint32_t n_keys, const uint8_t *key_bytes, const uint64_t *key_off) {
+  if (!g) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(g->mu);
+  for (size_t d = 0; d < g->ctx.size(); d++) {
+    bv_ctx *c = g->ctx[d];
+    if (!(c->flags & BV_F_KEY_CACHE)) return gfail(g, BV_E_ARGS, "group created without BV_F_KEY_CACHE");
+    if (hipSetDevice(c->device) != hipSuccess) return gfail(g, BV_E_NODEVICE, "hipSetDevice");
+    const int rc = bv_kc_register(c, n_keys, key_bytes, key_off);
+    if (rc != BV_OK) return gfail(g, rc, "device " + std::to_string(g->devices[d]) + ": " + c->err);
   }
   return BV_OK;
 }

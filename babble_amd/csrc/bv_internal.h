@@ -28,15 +28,22 @@
 
 #define KS_OK 0  // k_key_decode statuses (verify_core.h)
 
+struct EvjBases;
 namespace bvk {
 hipError_t sha256(hipStream_t, uint64_t, const uint8_t *, const uint64_t *, uint32_t *, uint64_t max_len = ~0ull);
 hipError_t put_digests(hipStream_t, uint64_t, const uint64_t *, const uint32_t *, uint32_t *);
 hipError_t key_decode(hipStream_t, uint32_t, const uint8_t *, const uint64_t *, uint8_t *, uint32_t *);
 hipError_t sha256_chain(hipStream_t, uint32_t, const uint8_t *, const uint64_t *, uint8_t *, uint32_t *);
 hipError_t ev_body_hash(hipStream_t st, const bv_event_batch &b, uint64_t e0, uint64_t e1, uint32_t *dig);
+// the same over a shard's slices (evjson.h EvjBases): [e0, e1) are the whole batch's event indices
+hipError_t ev_body_hash_rb(hipStream_t st, const bv_event_batch &b, uint64_t e0, uint64_t e1, const EvjBases &bs,
+                           uint32_t *dig);
 hipError_t iota(hipStream_t, uint64_t, uint32_t *);
 hipError_t sig_decode(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be, uint8_t *s_be,
                       uint8_t *pre);
+// `off` holds a larger batch's offsets and `text` starts at its byte `text_base`
+hipError_t sig_decode_rb(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint64_t text_base,
+                         uint8_t *r_be, uint8_t *s_be, uint8_t *pre);
 hipError_t build_tables(hipStream_t, int, uint32_t, const uint32_t *, const uint8_t *, uint32_t *, uint32_t *,
                         uint32_t *, uint32_t *, uint64_t n_items);
 hipError_t build_kc(hipStream_t, uint32_t, const uint32_t *, const uint8_t *, uint32_t *, uint32_t *, uint32_t *,
@@ -420,4 +427,18 @@ void bv_kc_release(bv_ctx *ctx);  // free every cached table (bv_destroy, after 
 // when they are bv_host_alloc memory (else bv_host_finish copies them).
 int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res = nullptr);
 int bv_host_finish(bv_ctx *ctx, const bv_batch *b, bv_result *res, bv_host_call *call, bool bits_out);
+// bv_verify_events' bulk path over one event range of a batch (bv_events.cpp):
+// events [a, z) and the parent hashes [hash_lo, hash_hi) its BV_PARENT_HASH
+// parents name (bv_plan_event_shards).  bv_validate_events checks the WHOLE
+// batch once; bv_events_launch enqueues the range's staging, hashing and
+// verify (`res`: the range's result pointers, reached by DMA when pinned) and
+// bv_events_finish collects after bv_mark_done, as bv_host_launch /
+// bv_host_finish do.  An empty range launches nothing (skip its finish).
+struct bv_ev_shard {
+  uint64_t a, z, hash_lo, hash_hi;
+};
+int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb);
+int bv_events_launch(bv_ctx *ctx, const bv_event_batch *eb, const bv_ev_shard &sh, const bv_result *res,
+                     bv_host_call *call);
+int bv_events_finish(bv_ctx *ctx, uint64_t n_events, bv_result *res, bv_host_call *call, bool bits_out);
 void bv_read_timing(bv_ctx *ctx);

@@ -159,15 +159,35 @@ DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
   return n;
 }
 
+// Bases of a shard (bv_group_verify_events): the arrays of `b` are the
+// slices one event range [a, z) of a larger batch needs, and the values in
+// them (tx_start, tx_off, itx_off, bsig_off, parent_ref) are still the whole
+// batch's.  Wherever such a value indexes another array, its base — the
+// value at which that slice starts — is subtracted:
+//   ev    a: the per-event arrays start at event a (e is the batch's index)
+//   tx    tx_start[a]: tx_off and tx_nil start at that transaction
+//   txb   tx_off[tx_start[a]]: tx_bytes starts at that byte
+//   itx   itx_off[a], bsig  bsig_off[a]: the fragment bytes start there
+//   ph    the first parent hash shipped: parent_hashes starts at hash `ph`
+// EvjNoBases (all zero, compile-time) is the whole batch: the subtractions
+// fold away and evj_emit compiles as it did without them.
+struct EvjBases {
+  uint64_t ev, tx, txb, itx, bsig, ph;
+};
+struct EvjNoBases {
+  static constexpr uint64_t ev = 0, tx = 0, txb = 0, itx = 0, bsig = 0, ph = 0;
+};
+
 // Event e's body into sink `o` (evj_len bytes).  In-batch parents get 64 '0'
 // placeholders, overwritten by evj_hex32 once the parent's digest exists.
-template <class O>
-DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o) {
+template <class O, class B = EvjNoBases>
+DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
+  e -= bs.ev;
   evj_lit(o, EVJ_L0);
   if (b.tx_list_nil && b.tx_list_nil[e]) {
     evj_lit(o, "null");
   } else {
-    const uint64_t t0 = b.tx_start[e], t1 = b.tx_start[e + 1];
+    const uint64_t t0 = b.tx_start[e] - bs.tx, t1 = b.tx_start[e + 1] - bs.tx;
     o.put('[');
     for (uint64_t t = t0; t < t1; t++) {
       if (t > t0) o.put(',');
@@ -175,7 +195,7 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o) {
         evj_lit(o, "null");
       } else {
         o.put('"');
-        evj_b64(o, b.tx_bytes + b.tx_off[t], b.tx_off[t + 1] - b.tx_off[t]);
+        evj_b64(o, b.tx_bytes + (b.tx_off[t] - bs.txb), b.tx_off[t + 1] - b.tx_off[t]);
         o.put('"');
       }
     }
@@ -184,7 +204,7 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o) {
   evj_lit(o, EVJ_L1);
   const uint64_t il = evj_frag_len(b.itx_off, e);
   if (il) {
-    for (uint64_t i = 0; i < il; i++) o.put(b.itx_json[b.itx_off[e] + i]);
+    for (uint64_t i = 0; i < il; i++) o.put(b.itx_json[b.itx_off[e] - bs.itx + i]);
   } else {
     evj_lit(o, "null");
   }
@@ -198,7 +218,7 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o) {
     }
     evj_lit(o, "\"0X");
     if (k == BV_PARENT_HASH) {
-      const uint8_t *d = b.parent_hashes + 32 * b.parent_ref[2 * e + p];
+      const uint8_t *d = b.parent_hashes + 32 * (b.parent_ref[2 * e + p] - bs.ph);
       for (int i = 0; i < 32; i++) {
         o.put(evj_hexc(d[i] >> 4));
         o.put(evj_hexc(d[i] & 15));
@@ -217,7 +237,7 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o) {
   evj_lit(o, EVJ_L5);
   const uint64_t bl = evj_frag_len(b.bsig_off, e);
   if (bl) {
-    for (uint64_t i = 0; i < bl; i++) o.put(b.bsig_json[b.bsig_off[e] + i]);
+    for (uint64_t i = 0; i < bl; i++) o.put(b.bsig_json[b.bsig_off[e] - bs.bsig + i]);
   } else {
     evj_lit(o, "null");
   }

@@ -6,10 +6,12 @@
 //                        stay on one device);
 //   bv_plan_group        the whole plan of bv_group_verify_batch: item order,
 //                        item shards, message partition;
-//   bv_merge_shard_bits  the accept bitmask from the all-gathered shard words.
+//   bv_merge_shard_bits  the accept bitmask from the all-gathered shard words;
+//   bv_plan_event_shards the plan of bv_group_verify_events: 64-aligned event
+//                        shards and each shard's range of parent hashes.
 //
-// Pure C++ so the same source links into the ASan/UBSan fuzz harness
-// (tests/hostfuzz) and into libbabbleverify.so.
+// Pure C++ so the same source links into the ASan/UBSan fuzz harnesses
+// (tests/hostfuzz, tests/hostfuzz_events) and into libbabbleverify.so.
 #include "hostplan.h"
 
 #include <algorithm>
@@ -59,6 +61,45 @@ extern "C" int bv_merge_shard_bits(const uint64_t *gathered, uint64_t words_per_
     }
   }
   return BV_OK;
+}
+
+// The plan of bv_group_verify_events.  Bulk batches (no BV_PARENT_EVENT
+// parent): contiguous event shards of whole 64-event words (the rule of
+// babble_amd/shard.py shard_bounds: ceil(words / n_shards) words each, the
+// last non-empty shard ends at n, trailing shards may be empty), and per
+// shard the range [hash_lo, hash_hi) of parent hashes its BV_PARENT_HASH
+// parents name (0, 0 without one).  A batch with in-batch parents stays whole
+// on shard 0: bounds {0, n, n, ...}, returns 1.
+extern "C" int bv_plan_event_shards(const bv_event_batch *b, int n_shards, uint64_t *event_bounds, uint64_t *hash_lo,
+                                    uint64_t *hash_hi) {
+  if (!b || n_shards <= 0 || !event_bounds || !hash_lo || !hash_hi) return BV_E_ARGS;
+  const uint64_t n = b->n_events;
+  if (n && (!b->parent_kind || !b->parent_ref)) return BV_E_ARGS;
+  const bool dag = n && memchr(b->parent_kind, BV_PARENT_EVENT, 2 * n) != nullptr;
+  plan_event_bounds(n, n_shards, dag, event_bounds);
+  for (int d = 0; d < n_shards; d++)
+    if (!event_hash_range(b, event_bounds[d], event_bounds[d + 1], &hash_lo[d], &hash_hi[d])) return BV_E_ARGS;
+  return dag ? 1 : 0;
+}
+
+void plan_event_bounds(uint64_t n, int D, bool dag, uint64_t *bounds) {
+  const uint64_t per = dag ? n : ((n + 63) / 64 + D - 1) / D * 64;
+  for (int d = 0; d <= D; d++) bounds[d] = (uint64_t)std::min<__uint128_t>(n, (__uint128_t)d * per);
+}
+
+bool event_hash_range(const bv_event_batch *b, uint64_t a, uint64_t z, uint64_t *lo_out, uint64_t *hi_out) {
+  uint64_t lo = UINT64_MAX, hi = 0;
+  for (uint64_t i = 2 * a; i < 2 * z; i++) {
+    if (b->parent_kind[i] > BV_PARENT_EVENT) return false;
+    if (b->parent_kind[i] != BV_PARENT_HASH) continue;
+    const uint64_t r = b->parent_ref[i];
+    if (r >= b->n_parent_hashes) return false;
+    lo = std::min(lo, r);
+    hi = std::max(hi, r + 1);
+  }
+  *lo_out = hi ? lo : 0;
+  *hi_out = hi;
+  return true;
 }
 
 static bool items_in_message_order(const bv_batch *b) {

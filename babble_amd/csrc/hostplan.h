@@ -21,3 +21,12 @@ struct GroupPlan {
 // `in_order`: whether item_msg is non-decreasing, when the caller already
 // knows (-1: checked here).
 void plan_group(const bv_batch *b, int D, GroupPlan &p, bv_batch &sorted, int in_order = -1);
+
+// The two halves of bv_plan_event_shards, for bv_group_verify_events (each
+// shard's host thread finds its own hash range, in pieces on its copy pool).
+// D + 1 event bounds: whole 64-event words per shard, or {0, n, n, ...} (dag).
+void plan_event_bounds(uint64_t n, int D, bool dag, uint64_t *bounds);
+// [lo, hi): from the smallest to the largest parent_ref among the
+// BV_PARENT_HASH parents of events [a, z) (0, 0 without one); false on an
+// unknown parent kind or a ref >= n_parent_hashes.
+bool event_hash_range(const bv_event_batch *b, uint64_t a, uint64_t z, uint64_t *lo, uint64_t *hi);

@@ -104,6 +104,23 @@ __global__ void __launch_bounds__(EVH_NT) k_ev_body_hash(bv_event_batch b, uint6
   dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
 }
 
+// The same over a shard (bv_group_verify_events): `b` holds the slices of
+// events [bs.ev, ...) of a larger batch, [e0, e1) are that batch's event
+// indices and `dig` is the shard's digest array (evjson.h EvjBases).
+__global__ void __launch_bounds__(EVH_NT) k_ev_body_hash_rb(bv_event_batch b, uint64_t e0, uint64_t e1, EvjBases bs,
+                                                            uint32_t *__restrict__ dig) {
+  __shared__ uint32_t rows[EVH_NT * EVH_ROW];
+  const uint64_t e = e0 + (uint64_t)blockIdx.x * EVH_NT + threadIdx.x;
+  if (e >= e1) return;  // no barriers below
+  EvjSha o = evj_sha_begin(rows + threadIdx.x * EVH_ROW);
+  evj_emit(b, e, o, bs);
+  uint32_t be[8];
+  evj_sha_finish(o, be);
+  uint4 *dst = (uint4 *)(dig + 8 * (e - bs.ev));
+  dst[0] = make_uint4(be[0], be[1], be[2], be[3]);
+  dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
+}
+
 // keys.DecodeSignature + the range checks on the device, one lane per event
 // (bv_event_batch sig_text): the same rules as bv_decode_signature
 // (hostparse.cpp, Go 1.13 strings.Split + big.Int.SetString(., 36)): exactly
@@ -163,12 +180,22 @@ DEV uint8_t sig_part36(const uint8_t *s, uint64_t len, uint8_t *out) {
 }
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_sig_decode(uint64_t n, const uint64_t *__restrict__ off,
-                                                     const uint8_t *__restrict__ text, uint8_t *__restrict__ r_be,
-                                                     uint8_t *__restrict__ s_be, uint8_t *__restrict__ pre) {
+// TB: the signature-text byte base of a shard (`off` holds the whole batch's
+// offsets, `text` starts at byte tb.v of it); SigNoBase is the whole batch.
+struct SigBase {
+  uint64_t v;
+};
+struct SigNoBase {
+  static constexpr uint64_t v = 0;
+};
+template <class TB>
+__device__ __forceinline__ void sig_decode_lane(uint64_t n, const uint64_t *__restrict__ off,
+                                                const uint8_t *__restrict__ text, const TB &tb,
+                                                uint8_t *__restrict__ r_be, uint8_t *__restrict__ s_be,
+                                                uint8_t *__restrict__ pre) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
-  const uint8_t *s = text + off[e];
+  const uint8_t *s = text + (off[e] - tb.v);
   const uint64_t len = off[e + 1] - off[e];
   uint64_t bar = len, parts = 1;
   for (uint64_t i = 0; i < len; i++)
@@ -184,6 +211,19 @@ __global__ void __launch_bounds__(256) k_sig_decode(uint64_t n, const uint64_t *
   }
   const uint8_t rc = sig_part36(s, bar, r), sc = sig_part36(s + bar + 1, len - bar - 1, sv);
   pre[e] = BV_PRE(rc, sc);
+}
+
+__global__ void __launch_bounds__(256) k_sig_decode(uint64_t n, const uint64_t *__restrict__ off,
+                                                     const uint8_t *__restrict__ text, uint8_t *__restrict__ r_be,
+                                                     uint8_t *__restrict__ s_be, uint8_t *__restrict__ pre) {
+  sig_decode_lane(n, off, text, SigNoBase{}, r_be, s_be, pre);
+}
+
+__global__ void __launch_bounds__(256) k_sig_decode_rb(uint64_t n, const uint64_t *__restrict__ off,
+                                                        const uint8_t *__restrict__ text, uint64_t text_base,
+                                                        uint8_t *__restrict__ r_be, uint8_t *__restrict__ s_be,
+                                                        uint8_t *__restrict__ pre) {
+  sig_decode_lane(n, off, text, SigBase{text_base}, r_be, s_be, pre);
 }
 
 __global__ void __launch_bounds__(256) k_iota(uint64_t n, uint32_t *__restrict__ out) {
@@ -1338,10 +1378,24 @@ hipError_t ev_body_hash(hipStream_t st, const bv_event_batch &b, uint64_t e0, ui
   return hipGetLastError();
 }
 
+hipError_t ev_body_hash_rb(hipStream_t st, const bv_event_batch &b, uint64_t e0, uint64_t e1, const EvjBases &bs,
+                           uint32_t *dig) {
+  if (e1 <= e0) return hipSuccess;
+  hipLaunchKernelGGL(k_ev_body_hash_rb, grid1(e1 - e0, EVH_NT), dim3(EVH_NT), 0, st, b, e0, e1, bs, dig);
+  return hipGetLastError();
+}
+
 hipError_t sig_decode(hipStream_t st, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be,
                       uint8_t *s_be, uint8_t *pre) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_sig_decode, grid1(n, 256), dim3(256), 0, st, n, off, text, r_be, s_be, pre);
+  return hipGetLastError();
+}
+
+hipError_t sig_decode_rb(hipStream_t st, uint64_t n, const uint64_t *off, const uint8_t *text, uint64_t text_base,
+                         uint8_t *r_be, uint8_t *s_be, uint8_t *pre) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sig_decode_rb, grid1(n, 256), dim3(256), 0, st, n, off, text, text_base, r_be, s_be, pre);
   return hipGetLastError();
 }
 

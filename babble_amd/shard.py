@@ -69,6 +69,29 @@ def plan_group(item_msg: np.ndarray, n_msgs: int, world: int):
     return permuted, perm, bounds, mb + [n_msgs]
 
 
+def plan_event_shards(parent_kind, parent_ref, n_shards: int):
+    """bv_plan_event_shards (csrc/hostplan.cpp) restated: (dag, bounds,
+    hash_lo, hash_hi).  A bulk batch (no parent of kind 2, an earlier event of
+    the batch) is cut by `shard_bounds`; shard d ships the parent hashes
+    [hash_lo[d], hash_hi[d]), from the smallest to the largest parent_ref among
+    its kind-1 (known hash) parents, (0, 0) without one.  A batch with
+    in-batch parents stays whole on shard 0: bounds [0, n, n, ...]."""
+    kind = np.asarray(parent_kind, dtype=np.uint8).reshape(-1, 2)
+    ref = np.asarray(parent_ref, dtype=np.uint64).reshape(-1, 2)
+    n = len(kind)
+    dag = bool(np.any(kind == 2))
+    if dag:
+        bounds = [0] + [n] * n_shards
+    else:
+        bounds = [shard_bounds(n, n_shards, d)[0] for d in range(n_shards)] + [n]
+    lo, hi = [], []
+    for d in range(n_shards):
+        r = ref[bounds[d]:bounds[d + 1]][kind[bounds[d]:bounds[d + 1]] == 1]
+        lo.append(int(r.min()) if r.size else 0)
+        hi.append(int(r.max()) + 1 if r.size else 0)
+    return dag, bounds, lo, hi
+
+
 def merge_bits(shard_words: Sequence[np.ndarray], bounds: Sequence[int]) -> np.ndarray:
     """Global accept bitmask from per-shard bitmasks whose bit 0 is the
     shard's first item (the host merge after bv_group's all-gather)."""

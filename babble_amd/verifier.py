@@ -347,6 +347,44 @@ class Group:
             raise native.BvError(rc, self._L.bv_group_last_error(self._g).decode(errors="replace"))
         return res
 
+    def _check(self, rc: int):
+        if rc != native.BV_OK:
+            raise native.BvError(rc, self._L.bv_group_last_error(self._g).decode(errors="replace"))
+
+    def verify_events(self, eb) -> VerifyResult:
+        """bv_group_verify_events over an events.EventWireBatch: a bulk batch
+        (no in-batch parent) is sharded by event index, each device building,
+        hashing and verifying its shard; a batch with in-batch parents runs
+        on device slot 0."""
+        keep: list = []
+        cb = eb.c_struct(keep)
+        n = eb.n_events
+        h = np.zeros((max(n, 1), 32), np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        bits = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        res = native.BvResult(h.ctypes.data, st.ctypes.data, bits.ctypes.data)
+        self._check(self._L.bv_group_verify_events(self._g, ctypes.byref(cb), ctypes.byref(res)))
+        return VerifyResult(h[:n], st[:n], bits[: (n + 63) // 64])
+
+    def verify_events_into(self, eb, res: VerifyResult) -> VerifyResult:
+        """bv_group_verify_events into caller-owned result arrays
+        (PinnedArena arrays are reached by DMA from every device; so are the
+        wire fields of a batch built by PinnedArena.wire)."""
+        keep: list = []
+        cb = eb.c_struct(keep)
+        r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
+        self._check(self._L.bv_group_verify_events(self._g, ctypes.byref(cb), ctypes.byref(r)))
+        return res
+
+    def register_keys(self, pubkeys: Sequence[bytes]) -> None:
+        """bv_group_kc_register: the validator set for every slot's key cache
+        (a group created with F_KEY_CACHE)."""
+        pubkeys = [bytes(k) for k in pubkeys]
+        buf = np.frombuffer(b"".join(pubkeys) or b"\0", np.uint8).copy()
+        off = np.zeros(len(pubkeys) + 1, np.uint64)
+        off[1:] = np.cumsum([len(k) for k in pubkeys], dtype=np.uint64)
+        self._check(self._L.bv_group_kc_register(self._g, len(pubkeys), buf.ctypes.data, off.ctypes.data))
+
     def timing(self, i: int = 0) -> dict:
         t = native.BvTiming()
         rc = self._L.bv_group_get_timing(self._g, i, ctypes.byref(t))
@@ -367,6 +405,21 @@ def plan_group(b: PackedBatch, n_shards: int):
     if rc < 0:
         raise native.BvError(rc, "bv_plan_group")
     return bool(rc), perm[: b.n_items], ib, mb
+
+
+def plan_event_shards(eb, n_shards: int):
+    """bv_plan_event_shards: (dag, event_bounds, hash_lo, hash_hi) — the plan
+    bv_group_verify_events follows for an events.EventWireBatch (host only)."""
+    keep: list = []
+    cb = eb.c_struct(keep)
+    bounds = np.zeros(n_shards + 1, np.uint64)
+    lo = np.zeros(max(n_shards, 1), np.uint64)
+    hi = np.zeros(max(n_shards, 1), np.uint64)
+    rc = native.lib().bv_plan_event_shards(ctypes.byref(cb), n_shards, bounds.ctypes.data, lo.ctypes.data,
+                                           hi.ctypes.data)
+    if rc < 0:
+        raise native.BvError(rc, "bv_plan_event_shards")
+    return bool(rc), bounds, lo[:n_shards], hi[:n_shards]
 
 
 def merge_shard_bits(gathered: np.ndarray, words_per_shard: int, bounds) -> np.ndarray:

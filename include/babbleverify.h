@@ -323,6 +323,48 @@ int bv_merge_shard_bits(const uint64_t *gathered, uint64_t words_per_shard, int 
 int bv_plan_group(const bv_batch *batch, int n_shards, uint64_t *item_bounds, uint64_t *msg_bounds,
                   uint32_t *perm);
 
+/* bv_verify_events over the group: events from their wire fields, sharded by
+ * event index.  The result contract is bv_verify_events' (msg_hash 32 * n
+ * bytes, status n bytes, accept_bits ceil(n / 64) words, any of them NULL;
+ * buffers in bv_host_alloc memory are reached by DMA in place), and so are
+ * the validation rules and their BV_E_ARGS cases, checked once over the whole
+ * batch; more than 2^32 events are BV_E_ARGS too.
+ * A batch without BV_PARENT_EVENT parents (a store / Bootstrap replay) is cut
+ * into contiguous event shards of whole 64-event words, one per device slot
+ * (bv_plan_event_shards).  Each slot stages, builds, hashes and verifies only
+ * its shard, concurrently, and writes its digests and statuses straight into
+ * the caller's buffers; the accept bitmasks come back through the same gather
+ * as bv_group_verify_batch's.  A shard ships the keys (whole), its slice of
+ * every per-event array, of the transactions, the fragments and the signature
+ * text, and the parent hashes [hash_lo, hash_hi) its BV_PARENT_HASH parents
+ * name.  The slices keep the caller's offsets and indices (nothing is
+ * rewritten on the host): the device subtracts the shard's bases.  A caller
+ * that lists parent_hashes in first-use order ships about 1 / n_devices of
+ * them per device; any other order is as correct but ships more (up to all of
+ * them to every device).
+ * A batch WITH in-batch parents (a SyncResponse DAG) is not sharded: it runs
+ * as one bv_verify_events call on device slot 0.
+ * After a failed call nothing stays in flight on any slot. */
+int bv_group_verify_events(bv_group *g, const bv_event_batch *events, bv_result *result);
+/* bv_kc_register on every slot's context (a BV_F_KEY_CACHE group's validator
+ * set; without it the slots' caches fill by the seen-twice rule only).
+ * Returns the first slot's failure, its text in bv_group_last_error;
+ * BV_E_ARGS on a group created without BV_F_KEY_CACHE. */
+int bv_group_kc_register(bv_group *g, uint32_t n_keys, const uint8_t *key_bytes, const uint64_t *key_off);
+/* Host helper (no device): the plan bv_group_verify_events follows.  Returns
+ * 0 for a batch without BV_PARENT_EVENT parents: event_bounds (n_shards + 1)
+ * are multiples of 64 except that the last non-empty shard ends at n_events
+ * (ceil(words / n_shards) 64-event words per shard; trailing shards may be
+ * empty), and [hash_lo[d], hash_hi[d]) spans the smallest to the largest
+ * parent_ref among shard d's BV_PARENT_HASH parents (0, 0 without one).
+ * Returns 1 for a batch with in-batch parents: event_bounds = {0, n, n, ...}
+ * and shard 0's hash range is computed the same way.  BV_E_ARGS on NULL
+ * pointers, n_shards <= 0, an unknown parent kind or a BV_PARENT_HASH ref >=
+ * n_parent_hashes.  Only n_events, parent_kind, parent_ref and
+ * n_parent_hashes are read. */
+int bv_plan_event_shards(const bv_event_batch *events, int n_shards, uint64_t *event_bounds, uint64_t *hash_lo,
+                         uint64_t *hash_hi);
+
 /* SHA-256 of n messages (host buffers) -> 32*n bytes. */
 int bv_sha256_batch(bv_ctx *ctx, uint64_t n_msgs, const uint8_t *msg_bytes,
                     const uint64_t *msg_off, uint8_t *out_hash);
