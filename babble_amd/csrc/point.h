@@ -270,7 +270,11 @@ DEV void gexz_set_ge(gexz &r, const fe &x, const fe &y) {
 }
 
 // r += (x2, y2) (affine), madd-2008-s: 8M + 2S + 6 add/sub.
-DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2) {
+// `xz_only` (wave-uniform): the caller reads only X and ZZ of the sum (the
+// last addition before final_check), so the common path stops after X3 and
+// leaves Y and ZZZ stale: 3M + 2 sub fewer.  The identity, doubling and
+// P + (-P) cases are complete either way.
+DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false) {
   if (inf) {
     gexz_set_ge(r, x2, y2);
     inf = false;
@@ -300,6 +304,7 @@ DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2) {
   fe_sub(t, t, PPP);
   fe_sub(t, t, Q);
   fe_sub(r.X, t, Q);
+  if (xz_only) return;
   // Y3 = R (Q - X3) - Y1 PPP, ZZZ3 = ZZZ1 PPP
   fe_sub(t, Q, r.X);
   fe_mul(t, R, t);
@@ -484,9 +489,9 @@ DEV void gexz_from_gej(gexz &r, const gej &a) {
 }
 
 template <bool LAT>
-DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2) {
-  if (LAT) gexz_add_ge_lat(r, inf, x2, y2);
-  else gexz_add_ge(r, inf, x2, y2);
+DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false) {
+  if (LAT) gexz_add_ge_lat(r, inf, x2, y2);  // latency variants always form the whole sum
+  else gexz_add_ge(r, inf, x2, y2, xz_only);
 }
 
 // r += (x2, y2) for r AFFINE (ZZ = ZZZ = 1, not the identity: the first
@@ -547,12 +552,13 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2) {
 // (scratch spills in the loop: k_verify_q +3 %), and the zipped latency
 // variants at 2-3 waves per SIMD run 10-15 % slower; this per-lane form
 // stays.
+// `xz_only`: see gexz_add_ge (XYZZ throughput form only; ignored elsewhere).
 template <bool LAT>
-DEV void pt_add_ge_step(gexz &r, bool &inf, const fe &x2, const fe &y2, bool take) {
-  if (take) pt_add_ge<LAT>(r, inf, x2, y2);
+DEV void pt_add_ge_step(gexz &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false) {
+  if (take) pt_add_ge<LAT>(r, inf, x2, y2, xz_only);
 }
 template <bool LAT>
-DEV void pt_add_ge_step(gej &r, bool &inf, const fe &x2, const fe &y2, bool take) {
+DEV void pt_add_ge_step(gej &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false) {
   if (take) gej_add_ge_sel<LAT>(r, inf, x2, y2);
 }
 template <bool LAT>

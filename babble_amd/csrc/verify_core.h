@@ -498,6 +498,131 @@ DEV bool final_check(const gexz &R, bool inf, const fe &r) {
   return false;
 }
 
+// ---------------------------------------------------------------------------
+// Table lookups one window ahead (throughput kernels).
+// BV_LOOKUP_PIPE (compile-time; bit 0: generator-table lookups, bit 1:
+// key-table lookups; default 3, 0 restores the load-then-add loops, so
+// tools/build_variant.sh builds A/B pairs from one tree): window j+1's
+// digit and entry address are formed, and its 64-byte entry requested,
+// before window j's addition starts, so the gather's latency runs under
+// ~1,800 VALU instructions instead of in front of them.
+// The entry lands in LDS, not in registers (the kernels sit at the 128 VGPRs
+// of 4 waves per SIMD): four 16-byte LDS-DMA loads per lane with a per-lane
+// source address; a wave-instruction writes its 64 lanes' chunks to 1 KiB at
+// a wave-uniform base, so chunk c of thread t is slot [c][t] of the block's
+// 16 KiB, and every lane reads back only what its own request wrote (no
+// barrier).  A lane requests only addresses its own loop will consume:
+// lanes that returned before the loop are masked off and issue nothing.
+// ---------------------------------------------------------------------------
+#ifndef BV_LOOKUP_PIPE
+#define BV_LOOKUP_PIPE 3
+#endif
+#define BV_STAGE_LANES 256  // threads per block of every throughput verify kernel
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ uint4 *entry_stage_slots() {
+  __shared__ uint4 slots[4 * BV_STAGE_LANES];
+  return slots;
+}
+#endif
+
+struct entry_stage {
+#if defined(__HIP_DEVICE_COMPILE__)
+  DEV void request(const uint32_t *e) {
+    typedef __attribute__((address_space(1))) uint4 *gptr;
+    typedef __attribute__((address_space(3))) uint4 *lptr;
+    // the slot's previous entry has left LDS (its ds_reads have returned)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const gptr g = (gptr)e;
+    const lptr w = (lptr)entry_stage_slots() + __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+      __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)(g + c),
+                                       (__attribute__((address_space(3))) void *)(w + c * BV_STAGE_LANES), 16, 0, 0);
+  }
+  DEV void take(fe &x, fe &y) {
+    // the four loads of the one request in flight; nothing else is
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint4 *s = entry_stage_slots() + threadIdx.x;
+    const uint4 a = s[0], b = s[BV_STAGE_LANES], c = s[2 * BV_STAGE_LANES], d = s[3 * BV_STAGE_LANES];
+    x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w;
+    x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
+    y.v[0] = c.x; y.v[1] = c.y; y.v[2] = c.z; y.v[3] = c.w;
+    y.v[4] = d.x; y.v[5] = d.y; y.v[6] = d.z; y.v[7] = d.w;
+  }
+#else
+  // host build (tests/emu): the same request / take order, the entry copied
+  // when it is requested
+  uint32_t buf[BV_ENTRY_U32];
+  DEV void request(const uint32_t *e) {
+    for (int k = 0; k < BV_ENTRY_U32; k++) buf[k] = e[k];
+  }
+  DEV void take(fe &x, fe &y) {
+    for (int k = 0; k < 8; k++) x.v[k] = buf[k], y.v[k] = buf[8 + k];
+  }
+#endif
+};
+
+// The second GLV half's magnitude waits in LDS while the first half is
+// summed (16 bytes per lane, read back by the lane that wrote them): four
+// VGPRs fewer live through the first half's additions, which pays for the
+// pipeline's own state (the next digit, the LDS address) within 128 VGPRs.
+struct lane_park {
+#if defined(__HIP_DEVICE_COMPILE__)
+  DEV uint4 *slot() {
+    __shared__ uint4 park[BV_STAGE_LANES];
+    return park + threadIdx.x;
+  }
+  DEV void put(const uint32_t v[4]) { *slot() = make_uint4(v[0], v[1], v[2], v[3]); }
+  DEV void get(uint32_t v[4]) {
+    const uint4 a = *slot();
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  }
+#else
+  uint32_t buf[4];
+  DEV void put(const uint32_t v[4]) {
+    for (int c = 0; c < 4; c++) buf[c] = v[c];
+  }
+  DEV void get(uint32_t v[4]) {
+    for (int c = 0; c < 4; c++) v[c] = buf[c];
+  }
+#endif
+};
+
+// kk = the magnitude of GLV half h (uniform): k1, or k2 (parked by the
+// caller with park.put(k2) when PARK).
+template <bool PARK>
+DEV void glv_half(uint32_t kk[4], int h, const uint32_t k1[4], const uint32_t k2[4], lane_park &park) {
+  if (PARK) {
+    if (h) park.get(kk);
+    else
+#pragma unroll
+      for (int c = 0; c < 4; c++) kk[c] = k1[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; c++) kk[c] = h ? k2[c] : k1[c];
+  }
+}
+
+// The next W-bit digit off the bottom of u (NL limbs, consumed).  SIGNED:
+// carry recoding into (-2^(W-1), 2^(W-1)]: returns |d| (0 when d == 2^W)
+// and dneg.
+template <int W, int NL, bool SIGNED>
+DEV uint32_t next_digit(uint32_t *u, uint32_t &carry, bool &dneg) {
+  constexpr uint32_t ENT = 1u << (W - 1);
+  uint32_t d = (u[0] & ((1u << W) - 1u)) + carry;
+#pragma unroll
+  for (int c = 0; c < NL - 1; c++) u[c] = (u[c] >> W) | (u[c + 1] << (32 - W));
+  u[NL - 1] >>= W;
+  dneg = false;
+  if (SIGNED) {
+    carry = d > ENT ? 1u : 0u;
+    dneg = carry != 0;
+    if (dneg) d = (1u << W) - d;
+  }
+  return d;
+}
+
 // R += sum_j T[j][digit_j(u)] over the 256-bit u1 (8 limbs, consumed:
 // shifted right W bits per window, so digits never straddle limbs) with
 // SIGNED digits in (-2^(W-1), 2^(W-1)] by carry recoding: T[j][|d|], y
@@ -506,11 +631,39 @@ DEV bool final_check(const gexz &R, bool inf, const fe &r) {
 // FROM_INF (XYZZ only): R enters as the identity, so after window 0 it is
 // that window's affine entry and window 1 adds with the 4M + 2S affine step
 // (gexz_add_ge_aff) — 4 multiplies fewer per item.
-template <int W, int NWIN, bool LAT = false, class PT = gej, bool FROM_INF = false>
+// FINAL: only X and ZZ of the sum are read afterwards (final_check), so the
+// top window's addition is the trimmed one (gexz_add_ge xz_only).
+template <int W, int NWIN, bool LAT = false, class PT = gej, bool FROM_INF = false, bool FINAL = false>
 DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8]) {
   constexpr uint32_t ENT = 1u << (W - 1);
   static_assert(W * NWIN >= 257 && W < 32, "signed G windows must absorb the last carry");
   uint32_t carry = 0;
+  if constexpr ((BV_LOOKUP_PIPE & 1) && !LAT && std::is_same<PT, gexz>::value) {
+    entry_stage stage;
+    bool dneg;
+    uint32_t d = next_digit<W, 8, true>(u, carry, dneg);
+    stage.request(tab + (uint64_t)d * BV_ENTRY_U32);  // d == 0: the window's slot 0, valid and not added
+#pragma unroll 1
+    for (int j = 0; j < NWIN; j++) {
+      fe x, y;
+      stage.take(x, y);
+      const uint32_t dj = d;
+      const bool nj = dneg;
+      if (j + 1 < NWIN) {  // the same recoding as the entry consumed next: never an address off the table
+        d = next_digit<W, 8, true>(u, carry, dneg);
+        stage.request(tab + ((uint64_t)(j + 1) * ENT + d) * BV_ENTRY_U32);
+      }
+      fe_cneg_canon(y, nj);
+      if constexpr (FROM_INF) {
+        if (j == 1 && !inf) {  // R = window 0's entry (affine)
+          if (dj != 0) gexz_add_ge_aff<LAT>(R, inf, x, y);
+          continue;
+        }
+      }
+      pt_add_ge_step<LAT>(R, inf, x, y, dj != 0, FINAL && j == NWIN - 1);
+    }
+    return;
+  }
   for (int j = 0; j < NWIN; j++) {
     uint32_t d = (u[0] & ((1u << W) - 1u)) + carry;
 #pragma unroll
@@ -532,7 +685,7 @@ DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8]) {
         continue;
       }
     }
-    pt_add_ge_step<LAT>(R, inf, x, y, d != 0);
+    pt_add_ge_step<LAT>(R, inf, x, y, d != 0, FINAL && j == NWIN - 1);
   }
 }
 
@@ -640,13 +793,48 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
 // (beta x, y): one multiply per lookup instead of a stored phi half (KC).
 // `from_inf` (uniform; XYZZ only): R enters as the identity, so window 1
 // adds to window 0's affine entry with the 4M + 2S step (as g_table_add).
+// `neg` (the half's sign) is folded into each entry's sign: adding the
+// negated entries to R gives the group element that negating R, adding the
+// entries and negating back gives, without the two field negations.
+// `last` (uniform; XYZZ throughput form): only X and ZZ of the sum are read
+// afterwards, so the top window's addition is the trimmed one.
 template <int W, int NWIN, bool SIGNED, bool LAT = false, class PT = gexz>
 DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], bool neg, bool phi = false,
-                       bool from_inf = false) {
+                       bool from_inf = false, bool last = false) {
   constexpr uint32_t ENT = SIGNED ? (1u << (W - 1)) : (1u << W);
   static_assert(!SIGNED || W * NWIN >= 129, "signed windows must absorb the last carry");
-  if (neg) fe_neg(R.Y, R.Y);
   uint32_t carry = 0;
+  if constexpr ((BV_LOOKUP_PIPE & 2) && !LAT && std::is_same<PT, gexz>::value) {
+    entry_stage stage;
+    bool dneg;
+    uint32_t d = next_digit<W, 4, SIGNED>(k, carry, dneg);
+    stage.request(tab + (uint64_t)d * BV_ENTRY_U32);  // d == 0: a valid, unused slot
+#pragma unroll 1
+    for (int j = 0; j < NWIN; j++) {
+      fe x, y;
+      stage.take(x, y);
+      const uint32_t dj = d;
+      const bool nj = dneg != neg;
+      if (j + 1 < NWIN) {  // the same recoding as the entry consumed next: never an address off the table
+        d = next_digit<W, 4, SIGNED>(k, carry, dneg);
+        stage.request(tab + ((uint64_t)(j + 1) * ENT + d) * BV_ENTRY_U32);
+      }
+      if (phi) {
+        fe beta;
+        fe_load(beta, FE_BETA);
+        fe_mul(x, x, beta);
+      }
+      fe_cneg_canon(y, nj);
+      if (from_inf && j == 1 && !inf) {  // R = window 0's entry (affine)
+        if (dj != 0) gexz_add_ge_aff<LAT>(R, inf, x, y);
+        continue;
+      }
+      pt_add_ge_step<LAT>(R, inf, x, y, dj != 0, last && j == NWIN - 1);
+    }
+    return;
+  }
+  constexpr bool fold = !LAT;  // the latency variants keep negating the accumulator around the half
+  if (!fold && neg) fe_neg(R.Y, R.Y);
   for (int j = 0; j < NWIN; j++) {
     uint32_t d = (k[0] & ((1u << W) - 1u)) + carry;
     k[0] = (k[0] >> W) | (k[1] << (32 - W));
@@ -670,16 +858,16 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
       fe_load(beta, FE_BETA);
       fe_mul(x, x, beta);
     }
-    fe_cneg_canon(y, dneg);
+    fe_cneg_canon(y, dneg != (fold && neg));
     if constexpr (std::is_same<PT, gexz>::value) {
       if (from_inf && j == 1 && !inf) {  // R = window 0's entry (affine)
         if (d != 0) gexz_add_ge_aff<LAT>(R, inf, x, y);
         continue;
       }
     }
-    pt_add_ge_step<LAT>(R, inf, x, y, d != 0);
+    pt_add_ge_step<LAT>(R, inf, x, y, d != 0, last && j == NWIN - 1);
   }
-  if (neg) fe_neg(R.Y, R.Y);
+  if (!fold && neg) fe_neg(R.Y, R.Y);
 }
 
 // Phase 2: R = R_G + k1 Q + k2 phi(Q) with the key's two half-tables;
@@ -709,12 +897,15 @@ DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, cons
   if (!tab) return BV_DEFERRED;  // key cache, partial batch: no table for this key
   // One loop body for both GLV halves (one inlined copy of the point
   // addition: smaller code, fewer live registers than two calls).
+  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+  lane_park park;
+  if (PARK) park.put(k2);
 #pragma unroll 1
   for (int h = 0; h < 2; h++) {
     uint32_t kk[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) kk[c] = h ? k2[c] : k1[c];
-    key_table_add<W, NWIN, SIGNED, LAT>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u, KC && h);
+    glv_half<PARK>(kk, h, k1, k2, park);
+    key_table_add<W, NWIN, SIGNED, LAT>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u, KC && h, false,
+                                        h == 1);
   }
   fe_load_be_words(r, r_be + 8 * i);  // reloaded: not kept live through the loop
   return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
@@ -759,11 +950,13 @@ DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, co
     rq[(uint64_t)32 * n + i] = 2u;
     return;
   }
+  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+  lane_park park;
+  if (PARK) park.put(k2);
 #pragma unroll 1
   for (int h = 0; h < 2; h++) {
     uint32_t kk[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) kk[c] = h ? k2[c] : k1[c];
+    glv_half<PARK>(kk, h, k1, k2, park);
     key_table_add<W, NWIN, SIGNED, LAT>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u, KC && h,
                                         h == 0);
   }
@@ -794,7 +987,7 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
   gexz R;
   bool inf;
   rg_load(rq, n, i, R, inf);
-  g_table_add<BV_GW, BV_GNWIN, LAT>(R, inf, g_table, u);
+  g_table_add<BV_GW, BV_GNWIN, LAT, gexz, false, true>(R, inf, g_table, u);
   fe_load_be_words(r, r_be + 8 * i);
   return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
 }
@@ -822,12 +1015,14 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
   fe_set(R.ZZ, 0);
   fe_set(R.ZZZ, 0);
   g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true>(R, inf, g_table, u);
+  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+  lane_park park;
+  if (PARK) park.put(k2);
 #pragma unroll 1
   for (int h = 0; h < 2; h++) {
     uint32_t kk[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) kk[c] = h ? k2[c] : k1[c];
-    key_table_add<BV_KCW, BV_KCNWIN, true, LAT>(R, inf, tab, kk, (signs >> h) & 1u, h != 0);
+    glv_half<PARK>(kk, h, k1, k2, park);
+    key_table_add<BV_KCW, BV_KCNWIN, true, LAT>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1);
   }
   fe_load_be_words(r, r_be + 8 * i);
   return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
