@@ -80,6 +80,10 @@ constexpr uint64_t kLatTableItems = 4096;
 #define BV_PREP_M 16
 #endif
 constexpr uint32_t kPrepM = BV_PREP_M;         // items per s^-1 batch
+#ifndef BV_PREP_LANES  // k_sinv lanes a batch spreads over before M grows (A/B: M = 32 at 1M items needs 32768)
+#define BV_PREP_LANES 65536
+#endif
+constexpr uint64_t kPrepLanes = BV_PREP_LANES;
 constexpr uint32_t kRgWords = 33;              // R_G words per item (XYZZ + inf: verify_core.h RG_WORDS)
 #ifndef BV_FUSED_KC
 #define BV_FUSED_KC 1
@@ -667,7 +671,8 @@ int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_
   // items per lane: kPrepM amortises the inversion in large batches; a small
   // batch spreads over ~64k lanes instead, since there the serial chain of
   // one lane (M products, the inversion, 2M products) is the latency
-  const uint32_t M = (uint32_t)std::min<uint64_t>(kPrepM, std::max<uint64_t>(1, (n_items + 65535) / 65536));
+  const uint32_t M =
+      (uint32_t)std::min<uint64_t>(kPrepM, std::max<uint64_t>(1, (n_items + kPrepLanes - 1) / kPrepLanes));
   HIPCHK(bvk::sinv(ctx->sstream, n_items, M, (const uint32_t *)b->s_be, b->pre, ctx->S().scratch.as<uint32_t>()),
          BV_E_LAUNCH, "k_sinv");
   // u2 = r s^-1 and its GLV split for k_verify_q, off k_verify_g's path

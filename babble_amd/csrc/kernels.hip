@@ -341,6 +341,52 @@ __global__ void __launch_bounds__(BLOCK) k_table_fill(const uint32_t *__restrict
   table_store(entry, PHI ? entry + half_u32 : nullptr, d, R, inf, zi);
 }
 
+// The K12 sub-tables from shared multiples (verify_core.h BV_FILL_SHARED),
+// throughput instantiation.  Step 1: grid (ceil(14 NSUB / 64), n_bases),
+// one multiple per lane into `mult` (the prefix scratch).
+template <int NSUB>
+__global__ void __launch_bounds__(64) k_fill_multiples(const uint32_t *__restrict__ bases_jac,
+                                                       const uint8_t *__restrict__ bstatus,
+                                                       uint32_t *__restrict__ mult) {
+  const uint32_t b = blockIdx.y, u = blockIdx.x * 64 + threadIdx.x;
+  if (bstatus && bstatus[b] != KS_OK) return;
+  if (u < (uint32_t)BV_FS_MULTS * NSUB) fill_multiple_one<NSUB>(b, u, bases_jac, mult);
+}
+
+// Step 2: grid (ceil(live / 64), n_bases); lane t of block c forms the live
+// entry f = 64 c + t of the key (lanes past the last one only join the
+// inversion) and the block normalises as k_table_fill does.
+template <int W, int L, int NSUB>
+__global__ void __launch_bounds__(64) k_table_fill_shared(const uint32_t *__restrict__ bases_jac,
+                                                          const uint8_t *__restrict__ bstatus,
+                                                          const uint32_t *__restrict__ mult,
+                                                          uint32_t *__restrict__ table) {
+  static_assert(L == 6, "the multiples are 3 + 3 bits");
+  constexpr uint32_t ODD = BV_FS_ODD_LIVE(W, L), LIVE = fs_live<L, NSUB, ODD>();
+  constexpr uint64_t key_u32 = (uint64_t)NSUB * (1ull << L) * BV_ENTRY_U32;
+  const uint32_t b = blockIdx.y, t = threadIdx.x, f = blockIdx.x * 64 + t;
+  if (bstatus && bstatus[b] != KS_OK) return;  // uniform per block
+  __shared__ fe sT[2 * 64 - 1];
+  const bool live = f < LIVE;
+  uint32_t k = 0, x = 0;
+  if (live) fill_shared_slot<L, NSUB, ODD>(f, k, x);
+  gej R;
+  bool inf = true;
+  fe Z;
+  fe_set(Z, 1);
+  if (live) {
+    fill_shared_point<NSUB>(R, inf, Z, b, k, x, mult);
+    if (!inf) {
+      fe bz;
+      fe_load(bz, bases_jac + ((uint64_t)b * NSUB + k) * 24 + 16);
+      fe_mul(Z, Z, bz);
+    }
+  }
+  fe zi = Z;
+  block_inverse<64>(sT, zi, t);  // Z_t^-1
+  if (live) table_store(table + (uint64_t)b * key_u32 + (((uint64_t)k << L) + x) * BV_ENTRY_U32, nullptr, x, R, inf, zi);
+}
+
 // K12 key tables from the 6-bit sub-tables (verify_core.h: pair_*).
 // One block of 256 threads per (window j, key): digit d = 256 e + t for
 // e < E (E = 2^(W-1) / 256; signed digits, geometry.h), so a wave shares hi
@@ -1525,7 +1571,18 @@ hipError_t build_tables(hipStream_t st, int kw, uint32_t n_bases, const uint32_t
     if (lat & 2)
       hipLaunchKernelGGL((k_table_fill<BV_K12L, BV_K12NSUB, false, 1 << BV_K12L, true>), dim3(BV_K12NSUB, n_bases),
                          dim3(1 << BV_K12L), 0, st, bases_jac, bstatus, sub);
-    else
+    else if (BV_FILL_SHARED) {
+      // the multiples live in `pscr` until k_table_pair (same stream) reuses it
+      constexpr uint32_t live = fs_live<BV_K12L, BV_K12NSUB, BV_FS_ODD_LIVE(BV_K12W, BV_K12L)>();
+      static_assert(BV_K12L == 6 && fs_mult_u32<BV_K12NSUB>() * 4 <= (uint64_t)BV_K12NWIN * BV_K12ENT * 32,
+                    "multiples fit the K12 prefix scratch");
+      hipLaunchKernelGGL((k_fill_multiples<BV_K12NSUB>), dim3((BV_FS_MULTS * BV_K12NSUB + 63) / 64, n_bases), dim3(64), 0,
+                         st, bases_jac, bstatus, pscr);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_table_fill_shared<BV_K12W, BV_K12L, BV_K12NSUB>), dim3((live + 63) / 64, n_bases), dim3(64),
+                         0, st, bases_jac, bstatus, pscr, sub);
+    } else
       hipLaunchKernelGGL((k_table_fill<BV_K12L, BV_K12NSUB, false, 1 << BV_K12L, false>), dim3(BV_K12NSUB, n_bases),
                          dim3(1 << BV_K12L), 0, st, bases_jac, bstatus, sub);
     e = hipGetLastError();

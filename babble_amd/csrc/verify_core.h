@@ -311,6 +311,103 @@ DEV void pair_store(uint32_t *entry, uint32_t *phi, int kind, const fe &x1, cons
 }
 
 // ---------------------------------------------------------------------------
+// K12 sub-tables from shared multiples (BV_FILL_SHARED, compile-time; 0
+// restores the per-entry double-and-add of k_table_fill for the throughput
+// instantiation, so tools/build_variant.sh builds A/B pairs from one tree).
+// k_table_fill forms every S_k[x] = x B_k, x < 2^L, by its own L-bit
+// double-and-add: ~5 doublings and ~3 additions per entry, and the chord
+// sums never read x > 2^(W-L-1) of the odd sub-tables (hi = d >> L of a
+// signed digit d <= 2^(W-1)).  Here, for L = 6:
+//   1. k_fill_multiples: per sub-table the 14 points m B_k, m = 1..7 and
+//      8, 16, .., 56 (one lane each, the same double-and-add; the tasks are
+//      ordered so that a wave holds multiples of one size), Jacobian on B_k's
+//      isomorphic curve as in k_table_fill, kept in the prefix scratch (free
+//      until k_table_pair);
+//   2. k_table_fill_shared: only the live entries, packed densely (64 per
+//      even sub-table, 33 per odd one), each ONE Jacobian addition
+//      (x & 7) B_k + (x >> 3) 8 B_k — distinct small multiples of a point of
+//      prime order, so never the doubling or the identity case — or a copy
+//      where one part is zero; then the same block_inverse and table_store.
+// The entries are canonical affine, so every byte k_table_pair reads is the
+// byte k_table_fill wrote (tests/test_fill_shared.py).
+// ---------------------------------------------------------------------------
+#ifndef BV_FILL_SHARED
+#define BV_FILL_SHARED 1
+#endif
+#define BV_FS_MULTS 14  // multiples per sub-table
+#define BV_FS_ODD_LIVE(W, L) ((1u << ((W) - (L) - 1)) + 1u)  // live entries of an odd sub-table
+
+// words of multiples scratch per key
+template <int NSUB>
+DEV constexpr uint64_t fs_mult_u32() { return (uint64_t)NSUB * BV_FS_MULTS * 24; }
+// live entries per key: all of the even sub-tables, ODD of the odd ones
+template <int L, int NSUB, uint32_t ODD>
+DEV constexpr uint32_t fs_live() { return (uint32_t)((NSUB + 1) / 2) * (1u << L) + (uint32_t)(NSUB / 2) * ODD; }
+
+// task u < 14 NSUB of key b: u < 7 NSUB the multiples 1..7, then 8..56
+template <int NSUB>
+DEV void fill_multiple_one(uint32_t b, uint32_t u, const uint32_t *bases_jac, uint32_t *mult) {
+  const bool big = u >= 7u * NSUB;
+  const uint32_t v = big ? u - 7u * NSUB : u, k = v / 7u, i = v % 7u;
+  const uint32_t *bj = bases_jac + ((uint64_t)b * NSUB + k) * 24;
+  fe bx, by, Z;
+  fe_load(bx, bj);
+  fe_load(by, bj + 8);
+  gej R;
+  bool inf;
+  table_point<false>(R, inf, Z, bx, by, big ? 8u * (i + 1) : i + 1, 6);
+  uint32_t *o = mult + (uint64_t)b * fs_mult_u32<NSUB>() + ((uint64_t)k * BV_FS_MULTS + (big ? 7u : 0u) + i) * 24;
+  fe_store(o, R.X);
+  fe_store(o + 8, R.Y);
+  fe_store(o + 16, Z);
+}
+
+// live entry f < fs_live() of a key -> sub-table k and entry x
+template <int L, int NSUB, uint32_t ODD>
+DEV void fill_shared_slot(uint32_t f, uint32_t &k, uint32_t &x) {
+  constexpr uint32_t EVEN = (uint32_t)((NSUB + 1) / 2) << L;
+  if (f < EVEN) {
+    k = 2u * (f >> L);
+    x = f & ((1u << L) - 1u);
+  } else {
+    k = 2u * ((f - EVEN) / ODD) + 1u;
+    x = (f - EVEN) % ODD;
+  }
+}
+
+// x B_k (Jacobian on B_k's isomorphic curve; inf for x == 0) from the multiples
+template <int NSUB>
+DEV void fill_shared_point(gej &R, bool &inf, fe &Z, uint32_t b, uint32_t k, uint32_t x, const uint32_t *mult) {
+  const uint32_t l = x & 7u, h = x >> 3;
+  const uint32_t *mk = mult + (uint64_t)b * fs_mult_u32<NSUB>() + (uint64_t)k * BV_FS_MULTS * 24;
+  inf = x == 0;
+  fe_set(R.X, 0);
+  fe_set(R.Y, 0);
+  fe_set(R.Z, 1);
+  if (l) {
+    const uint32_t *p = mk + (l - 1u) * 24;
+    fe_load(R.X, p);
+    fe_load(R.Y, p + 8);
+    fe_load(R.Z, p + 16);
+  }
+  if (h) {
+    const uint32_t *p = mk + (7u + h - 1u) * 24;
+    gej H;
+    fe_load(H.X, p);
+    fe_load(H.Y, p + 8);
+    fe_load(H.Z, p + 16);
+    if (l) {
+      bool ri = false;
+      gej_add(R, ri, H, false);
+      inf = ri;  // (cannot happen: see above)
+    } else {
+      R = H;
+    }
+  }
+  Z = R.Z;
+}
+
+// ---------------------------------------------------------------------------
 // Scalars: u1 = e * s^-1, u2 = r * s^-1 (mod N)  (ecdsa.Verify steps 4-6)
 // ---------------------------------------------------------------------------
 DEV void sc_sqrn(sc &a, int n) {

@@ -20,7 +20,7 @@ for d in sorted(glob.glob(os.path.join(root, "pmcab_*"))):
             for row in csv.DictReader(f):
                 low = {k.lower(): x for k, x in row.items()}
                 name = low.get("kernel_name", "?").split("(")[0].replace("void ", "").strip()
-                if "k_verify" not in name and "k_sha256" != name and "k_sinv" != name:
+                if not any(t in name for t in ("k_verify", "k_sha256", "k_sinv", "k_glv_split", "k_table_", "k_fill_")):
                     continue
                 did = low.get("dispatch_id")
                 try:
