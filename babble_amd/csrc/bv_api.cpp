@@ -524,6 +524,7 @@ extern "C" int bv_create(bv_ctx **out, int device, uint32_t flags) {
   if (!out) return BV_E_ARGS;
   *out = nullptr;
   if (flags & ~BV_F_KNOWN) return BV_E_ARGS;
+  if ((flags & BV_F_KC_COMPACT) && !(flags & BV_F_KEY_CACHE)) return BV_E_ARGS;  // a geometry of the cache
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BV_E_NODEVICE;
   if (device < 0) {
@@ -631,7 +632,7 @@ int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_
   const uint64_t min_items = n_keys <= kManyKeys ? ctx->table_min_items : ctx->table_min_items_many;
   const bool table_mode = kc || (n_keys <= kMaxTableKeys && n_items >= min_items * n_keys) ||
                           (n_keys <= ctx->lat_table_keys && n_items <= kLatTableItems && n_items > 0);
-  const int key_w = kc ? BV_KCW
+  const int key_w = kc ? ctx->kc_w  // the context's cached geometry: 22 (KC) or 18 (KC18)
                     : !table_mode ? 0
                     : (n_keys <= kMaxK12Keys && n_items >= ctx->k12_min_items * n_keys && !(ctx->flags & BV_F_K8))
                         ? 12
@@ -738,8 +739,8 @@ int bv_launch_items(bv_ctx *ctx, const bv_batch *b, const bv_out &o, hipStream_t
     return BV_OK;
   }
   if (fused)
-    HIPCHK(bvk::verify_gq(st, n, lo, hi, b->item_key, r32, s32, b->pre, kst, b->item_msg, o.dig, w, ctx->g_table,
-                          ctx->S().kc_tabs.as<uint64_t>(), o.status, o.bits),
+    HIPCHK(bvk::verify_gq(st, ctx->key_w, n, lo, hi, b->item_key, r32, s32, b->pre, kst, b->item_msg, o.dig, w,
+                          ctx->g_table, ctx->S().kc_tabs.as<uint64_t>(), o.status, o.bits),
            BV_E_LAUNCH, "k_verify_gq");
   else if (ctx->table_mode)
     HIPCHK(bvk::verify_q(st, ctx->key_w, n, lo, hi, b->item_key, r32, s32, b->pre, kst, u12,

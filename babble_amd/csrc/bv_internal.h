@@ -46,13 +46,16 @@ hipError_t sig_decode_rb(hipStream_t, uint64_t n, const uint64_t *off, const uin
                          uint8_t *r_be, uint8_t *s_be, uint8_t *pre);
 hipError_t build_tables(hipStream_t, int, uint32_t, const uint32_t *, const uint8_t *, uint32_t *, uint32_t *,
                         uint32_t *, uint32_t *, uint64_t n_items);
-hipError_t build_kc(hipStream_t, uint32_t, const uint32_t *, const uint8_t *, uint32_t *, uint32_t *, uint32_t *,
-                    const uint64_t *);
-size_t kc_pscr_bytes();
+// kw: the cached geometry, 22 (KC) or 18 (KC18); any other value is hipErrorInvalidValue
+hipError_t build_kc(hipStream_t, int kw, uint32_t, const uint32_t *, const uint8_t *, uint32_t *, uint32_t *,
+                    uint32_t *, const uint64_t *);
+size_t kc_table_bytes(int kw);  // one cached table
+size_t kc_sub_bytes(int kw);    // build scratch per key: sub-tables
+size_t kc_pscr_bytes(int kw);   //   and prefix products
 hipError_t sinv(hipStream_t, uint64_t, uint32_t, const uint32_t *, const uint8_t *, uint32_t *);
 hipError_t glv_split(hipStream_t, uint64_t n, const uint32_t *r_be, const uint32_t *w, uint32_t *u12);
 // verify kernels over items [lo, hi) of an n-item batch (lo a multiple of 64)
-hipError_t verify_gq(hipStream_t, uint64_t, uint64_t, uint64_t, const uint32_t *, const uint32_t *, const uint32_t *,
+hipError_t verify_gq(hipStream_t, int kw, uint64_t, uint64_t, uint64_t, const uint32_t *, const uint32_t *, const uint32_t *,
                      const uint8_t *, const uint8_t *, const uint32_t *, const uint32_t *, const uint32_t *,
                      const uint32_t *, const uint64_t *, uint8_t *, uint64_t *);
 // list: n + 1 words (the deferred items' indices, then their count)
@@ -295,9 +298,14 @@ struct bv_ctx {
   hipEvent_t ev_host = nullptr;  // host waits on this ctx's own work on a shared lane (bv_host_wait)
   bool has_done = false;
   bool table_mode = false;
-  int key_w = 0;  // 8, 12 or 20 (KC) in table mode
+  int key_w = 0;  // 8, 12 or kc_w (key cache) in table mode
   bv_timing timing = {};
   // key cache (BV_F_KEY_CACHE, bv_keycache.cpp)
+  // The ONE cached geometry of this context, fixed at bv_create: 22 (KC, 805
+  // MB per key) or, with BV_F_KC_COMPACT, 18 (KC18, 67.1 MB per key).
+  int kc_w = BV_KCW;
+  uint64_t kc_table_bytes = 0, kc_sub_bytes = 0, kc_pscr_bytes = 0;  // per key, of kc_w (bv_kc_init)
+  uint32_t kc_build_group = 0;  // keys per table-build launch (bounds the build scratch)
   std::unordered_map<std::string, int> kc_index;  // keys whose table build has been enqueued
   std::vector<KcSlot> kc_slots;
   std::unordered_set<std::string> kc_registered;  // bv_kc_register: the validator set

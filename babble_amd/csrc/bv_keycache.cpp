@@ -1,8 +1,10 @@
 // bv_keycache.cpp — the key cache of a bv_ctx (BV_F_KEY_CACHE): per-validator
-// KC tables (22-bit signed GLV windows, 805 MB each) kept in HBM across calls,
-// keyed by the raw pubkey bytes.  Babble's validator set is stable
-// (src/peers/peer_set.go), so the tables of the PeerSet's keys are built once
-// and every later batch of their events skips the per-batch table build.
+// KC tables (22-bit signed GLV windows, 805 MB each; with BV_F_KC_COMPACT the
+// KC18 geometry, 18-bit windows, 67.1 MB each — one geometry per context,
+// fixed at bv_create) kept in HBM across calls, keyed by the raw pubkey bytes.
+// Babble's validator set is stable (src/peers/peer_set.go), so the tables of
+// the PeerSet's keys are built once and every later batch of their events
+// skips the per-batch table build.
 //
 // Invariants:
 //  * kc_index maps a key ONLY to a slot whose table build has been enqueued
@@ -39,10 +41,15 @@
   } while (0)
 
 namespace {
-constexpr uint64_t kKcTableBytes = BV_KCTABLE_U32 * 4;  // 805 MB per cached key
-constexpr uint64_t kKcSubBytes = BV_KCSUB_U32 * 4;
-constexpr uint32_t kKcBases = 22;       // bases_jac allocation per key (>= BV_KCNSUB)
-constexpr uint32_t kKcBuildGroup = 8;   // keys per KC build launch (pscr: 403 MB per key)
+// The table, sub-table and prefix-scratch sizes are the context's geometry's
+// (ctx->kc_table_bytes, kc_sub_bytes, kc_pscr_bytes: 805 MB / 1.5 MB / 403 MB
+// per key for KC, 67.1 MB / 0.5 MB / 33.5 MB for KC18).
+constexpr uint32_t kKcBases = 22;       // bases_jac allocation per key (>= BV_KCNSUB, BV_KC18NSUB)
+constexpr uint32_t kKcBuildGroup = 8;   // KC: keys per build launch (3.2 GB of scratch)
+// KC18: 64 keys per launch = 2.2 GB of scratch, under KC's 3.2 GB, and 16384
+// blocks per k_table_pair_kc launch; 1000 registered keys build in 16
+// launch / wait rounds, not 125.
+constexpr uint32_t kKc18BuildGroup = 64;
 constexpr size_t kKcMemoMax = 4096;     // entries of kc_seen / kc_bad
 constexpr uint64_t kKcPartialRatio = 16;  // partial batches: at most 1 valid key in 16 without a table
 
@@ -56,7 +63,12 @@ void memo_insert(Set &s, const std::string &k) {
 }  // namespace
 
 void bv_kc_init(bv_ctx *ctx) {
-  double gb = 96.0;  // 119 KC tables: C5's 100 validators fit
+  ctx->kc_w = (ctx->flags & BV_F_KC_COMPACT) ? BV_KC18W : BV_KCW;
+  ctx->kc_table_bytes = bvk::kc_table_bytes(ctx->kc_w);
+  ctx->kc_sub_bytes = bvk::kc_sub_bytes(ctx->kc_w);
+  ctx->kc_pscr_bytes = bvk::kc_pscr_bytes(ctx->kc_w);
+  ctx->kc_build_group = ctx->kc_w == BV_KC18W ? kKc18BuildGroup : kKcBuildGroup;
+  double gb = 96.0;  // 119 KC tables (C5's 100 validators fit) or 1430 KC18 tables
   if (const char *s = getenv("BV_KEY_CACHE_GB")) gb = atof(s);
   ctx->kc_budget = (uint64_t)(std::max(gb, 0.0) * 1e9);
   if (const char *s = getenv("BV_KC_ADMIT")) ctx->kc_admit = (uint32_t)std::max(1, atoi(s));
@@ -78,7 +90,7 @@ void bv_kc_release(bv_ctx *ctx) {
 
 static hipError_t kc_table_alloc(bv_ctx *ctx, void **p) {
   if (++ctx->kc_allocs == (uint64_t)ctx->kc_fail_alloc) return hipErrorOutOfMemory;  // injected
-  hipError_t e = hipMalloc(p, kKcTableBytes);
+  hipError_t e = hipMalloc(p, ctx->kc_table_bytes);
   if (e != hipSuccess) (void)hipGetLastError();
   return e;
 }
@@ -216,7 +228,7 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
   // Registration builds as many registered keys as the budget holds (in the
   // caller's order); the rest stay uncached (timing.kc_keys tells).  A
   // batch whose own keys alone exceed the budget takes the per-batch path.
-  const uint64_t fit = ctx->kc_budget / kKcTableBytes;
+  const uint64_t fit = ctx->kc_budget / ctx->kc_table_bytes;
   if (admit.size() > fit) {
     if (!force_build) return bail();
     admit.resize(fit);
@@ -231,7 +243,7 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
       HIPCHK(hipEventRecord(ctx->S().ev[E_KCDEC], st), BV_E_LAUNCH, "event");
       ctx->S().kc_decoded = true;  // ordered before the builds and the verify on `st`; sstream waits (bv_run_keys)
     }
-    const uint64_t need = (uint64_t)admit.size() * kKcTableBytes;
+    const uint64_t need = (uint64_t)admit.size() * ctx->kc_table_bytes;
     bool all_registered = true;
     for (uint32_t k : admit) all_registered = all_registered && ctx->kc_registered.count(key_of(k));
     // evict least-recently-used tables this batch does not use: unregistered
@@ -257,7 +269,7 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
       ctx->kc_index.erase(s.bytes);
       s = KcSlot{};
       s.free = true;
-      ctx->kc_bytes -= kKcTableBytes;
+      ctx->kc_bytes -= ctx->kc_table_bytes;
     }
     // Allocate this call's slots.  They are indexed only after their build
     // is enqueued; `rollback` frees them on any failure.
@@ -269,7 +281,7 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
         auto &s = ctx->kc_slots[si];
         if (s.table) {
           (void)hipFree(s.table);
-          ctx->kc_bytes -= kKcTableBytes;
+          ctx->kc_bytes -= ctx->kc_table_bytes;
         }
         s = KcSlot{};
         s.free = true;
@@ -297,21 +309,21 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
         rollback();
         return bail();  // HBM exhausted: per-batch path for this call, nothing indexed
       }
-      ctx->kc_bytes += kKcTableBytes;
+      ctx->kc_bytes += ctx->kc_table_bytes;
       slot_of[k] = si;
     }
-    // build the new tables, kKcBuildGroup keys per launch
+    // build the new tables, kc_build_group keys per launch
     auto fail = [&](int code, const char *what, hipError_t e) {
       rollback();
       return bv_fail(ctx, code, what, e);
     };
-    const uint32_t G = std::min<uint32_t>(kKcBuildGroup, (uint32_t)admit.size());
+    const uint32_t G = std::min<uint32_t>(ctx->kc_build_group, (uint32_t)admit.size());
     hipError_t e;
     if ((e = ctx->kc_kxy.ensure((uint64_t)G * 64)) != hipSuccess ||
         (e = ctx->kc_btabs.ensure((uint64_t)G * 8)) != hipSuccess ||
         (e = ctx->S().bases_jac.ensure((uint64_t)G * kKcBases * 96)) != hipSuccess ||
-        (e = ctx->S().key_sub.ensure((uint64_t)G * kKcSubBytes)) != hipSuccess ||
-        (e = ctx->S().key_pscr.ensure((uint64_t)G * bvk::kc_pscr_bytes())) != hipSuccess ||
+        (e = ctx->S().key_sub.ensure((uint64_t)G * ctx->kc_sub_bytes)) != hipSuccess ||
+        (e = ctx->S().key_pscr.ensure((uint64_t)G * ctx->kc_pscr_bytes)) != hipSuccess ||
         (e = ctx->S().pin_small.ensure(4096)) != hipSuccess)
       return fail(BV_E_OOM, "alloc KC build scratch", e);
     for (size_t g0 = 0; g0 < admit.size(); g0 += G) {
@@ -330,9 +342,9 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
       launched = true;
       e = ++ctx->kc_build_calls == (uint64_t)ctx->kc_fail_build
               ? hipErrorLaunchFailure  // injected
-              : bvk::build_kc(st, n, ctx->kc_kxy.as<uint32_t>(), nullptr, ctx->S().bases_jac.as<uint32_t>(),
-                              ctx->S().key_sub.as<uint32_t>(), ctx->S().key_pscr.as<uint32_t>(),
-                              ctx->kc_btabs.as<uint64_t>());
+              : bvk::build_kc(st, ctx->kc_w, n, ctx->kc_kxy.as<uint32_t>(), nullptr,
+                              ctx->S().bases_jac.as<uint32_t>(), ctx->S().key_sub.as<uint32_t>(),
+                              ctx->S().key_pscr.as<uint32_t>(), ctx->kc_btabs.as<uint64_t>());
       if (e != hipSuccess) return fail(BV_E_LAUNCH, "KC key tables", e);
       builds += n;
     }
@@ -365,8 +377,15 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
 // Host-only lookup for the small-batch path (no device work, no sync): the
 // table of every batch key that has one built, else 0.  Small batches never
 // build tables (registration and bulk batches do).  Returns the hits.
+// k_small's warm tree has one leaf per KC window (kSmallLeaves), so a KC18
+// context gives it no tables and 0 hits: its small batches run as for keys
+// without a table, and the tables serve the bulk pipeline.
 uint32_t bv_kc_lookup(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko, uint64_t *tabs) {
   uint32_t hits = 0;  // distinct keys, as bv_kc_prepare counts them
+  if (ctx->kc_w != BV_KCW) {
+    for (uint32_t k = 0; k < n_keys; k++) tabs[k] = 0;
+    return 0;
+  }
   const uint64_t clock = ++ctx->kc_clock;
   for (uint32_t k = 0; k < n_keys; k++) {
     tabs[k] = 0;
@@ -381,8 +400,10 @@ uint32_t bv_kc_lookup(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const ui
   return hits;
 }
 
-// Every well-formed key of the batch has a built table (host-only).
+// Every well-formed key of the batch has a built table that k_small can
+// read (host-only): never on a KC18 context (bv_kc_lookup).
 bool bv_kc_all_cached(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko) {
+  if (ctx->kc_w != BV_KCW) return false;
   for (uint32_t k = 0; k < n_keys; k++) {
     if (!key_form_ok(hkb + hko[k], hko[k + 1] - hko[k])) continue;
     if (!ctx->kc_index.count(std::string((const char *)hkb + hko[k], (size_t)(hko[k + 1] - hko[k])))) return false;

@@ -73,5 +73,24 @@
 #define BV_KCTABLE_U32 BV_KCHALF_U32  // no stored phi half
 #define BV_KCSUB_U32 ((uint64_t)BV_KCNSUB * (1ull << BV_KCL) * BV_ENTRY_U32)
 #define BV_KCPAIR_ENT 4096  // entries per k_table_pair_kc block (16 per thread)
+// KC18: the compact key-cache geometry (BV_F_KEY_CACHE | BV_F_KC_COMPACT), for
+// validator sets the 805 MB tables cannot hold (119 keys in 96 GB): 18-bit
+// signed-digit windows x 8 (144 bits >= 129) = 16 adds + 8 multiplies per
+// item for u2 Q, 67.1 MB per key (1430 keys in 96 GB).  The same layout as
+// KC: one stored half, phi(T) formed per lookup, digit 2^17 of window j in
+// slot 0 of window j+1, one pad entry after the top window.  Entries are
+// chord sums of two 9-bit sub-table points S_k[x] = x 2^(9 k) Q, k < 16.
+#define BV_KC18W 18
+#define BV_KC18NWIN 8
+#define BV_KC18L 9
+#define BV_KC18NSUB 16
+#define BV_KC18ENT (1u << (BV_KC18W - 1))
+#define BV_KC18HALF_U32 (((uint64_t)BV_KC18NWIN * BV_KC18ENT + 1) * BV_ENTRY_U32)
+#define BV_KC18TABLE_U32 BV_KC18HALF_U32  // no stored phi half
+#define BV_KC18SUB_U32 ((uint64_t)BV_KC18NSUB * (1ull << BV_KC18L) * BV_ENTRY_U32)
+// A cached geometry: one stored half per key, phi(T) = (beta x, y) formed per
+// lookup, per-key table base addresses (key_tabs) instead of one contiguous
+// per-batch allocation.
+#define BV_W_IS_CACHED(W) ((W) == BV_KCW || (W) == BV_KC18W)
 // per-item GLV halves of u2 (k_verify_g -> k_verify_q): k1[4] | k2[4] | signs | pad
 #define BV_U_STRIDE 12

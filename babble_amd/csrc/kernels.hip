@@ -14,7 +14,8 @@
 //                (12-bit signed, GLV) tables; decision table; X == r ZZ;
 //                status + __ballot accept bits
 // Key cache (BV_F_KEY_CACHE): the validator's KC tables (22-bit signed
-// windows, built once by k_table_pair_kc) replace the keys stream and
+// windows x 6, or with BV_F_KC_COMPACT the KC18 geometry, 18-bit x 8; built
+// once by k_table_pair_kc) replace the keys stream and
 // k_verify_gq does g + q in one pass.  k_verify_generic covers keys with too
 // few items for a table.  The G table (k_table_pair_g, 21.5 GB) is built once
 // per process and device.  Host batches of <= 256 items take k_small (one
@@ -665,7 +666,7 @@ __global__ void __launch_bounds__(256, LAT ? BV_LWAVES : BV_QWAVES) k_verify_gf(
 #ifndef BV_GQWAVES
 #define BV_GQWAVES BV_QWAVES
 #endif
-template <bool LAT>
+template <int W, int NWIN, bool LAT>
 __global__ void __launch_bounds__(256, LAT ? BV_LWAVES : BV_GQWAVES) k_verify_gq(uint64_t n_items, uint64_t lo, uint64_t hi,
                                                    const uint32_t *__restrict__ item_key,
                                                    const uint32_t *__restrict__ r_be, const uint32_t *__restrict__ s_be,
@@ -679,11 +680,13 @@ __global__ void __launch_bounds__(256, LAT ? BV_LWAVES : BV_GQWAVES) k_verify_gq
   const uint64_t i = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint8_t st = BV_REJECT;
   if (i < hi)
-    st = verify_item_gq_kc<LAT>(i, item_key, r_be, s_be, pre, kstatus, item_msg, digest_words, w_in, g_table, key_tabs);
+    st = verify_item_gq_kc<W, NWIN, LAT>(i, item_key, r_be, s_be, pre, kstatus, item_msg, digest_words, w_in, g_table,
+                                         key_tabs);
   write_status(i, hi, st, status, bits);
 }
 
-// Key-cache (KC) table windows from the 11-bit sub-tables: block (c, key)
+// Key-cache table windows from the L-bit sub-tables (KC: <22, 11, 6>, KC18:
+// <18, 9, 8>; 2 L = W, two sub-tables per window): block (c, key)
 // holds slots s = BV_KCPAIR_ENT c' + 256 e + t (e < 16) of window
 // j = c / (ENT / BV_KCPAIR_ENT), c' = c mod that; digit k12_digit(s) (signed
 // windows: slot 0 builds digit ENT, stored in window j+1's slot 0).  A wave
@@ -1621,8 +1624,9 @@ hipError_t verify_g(hipStream_t st, uint64_t n, uint64_t lo, uint64_t hi, const 
   return hipGetLastError();
 }
 
-// kw = 8 / 12: contiguous per-batch tables in key_table; kw = 22: the key
-// cache (KC), table base address per batch key in key_tabs.
+// kw = 8 / 12: contiguous per-batch tables in key_table; kw = 22 / 18: the
+// key cache (KC / KC18), table base address per batch key in key_tabs.  Any
+// other kw is an error: no kernel runs.
 hipError_t verify_q(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t hi, const uint32_t *item_key,
                     const uint32_t *r_be, const uint32_t *s_be, const uint8_t *pre, const uint8_t *kst,
                     const uint32_t *u12, const uint32_t *key_table, const uint64_t *key_tabs, const uint32_t *rg,
@@ -1640,8 +1644,12 @@ hipError_t verify_q(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t hi
     BV_LAUNCH_Q(BV_KW, BV_KNWIN, key_table, nullptr)
   } else if (kw == 12) {
     BV_LAUNCH_Q(BV_K12W, BV_K12NWIN, key_table, nullptr)
-  } else {
+  } else if (kw == BV_KCW) {
     BV_LAUNCH_Q(BV_KCW, BV_KCNWIN, nullptr, key_tabs)
+  } else if (kw == BV_KC18W) {
+    BV_LAUNCH_Q(BV_KC18W, BV_KC18NWIN, nullptr, key_tabs)
+  } else {
+    return hipErrorInvalidValue;  // an unknown geometry never reads a table
   }
 #undef BV_LAUNCH_Q
   return hipGetLastError();
@@ -1665,8 +1673,12 @@ hipError_t verify_qf(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t h
     BV_LAUNCH_QF(BV_KW, BV_KNWIN, key_table, nullptr)
   } else if (kw == 12) {
     BV_LAUNCH_QF(BV_K12W, BV_K12NWIN, key_table, nullptr)
-  } else {
+  } else if (kw == BV_KCW) {
     BV_LAUNCH_QF(BV_KCW, BV_KCNWIN, nullptr, key_tabs)
+  } else if (kw == BV_KC18W) {
+    BV_LAUNCH_QF(BV_KC18W, BV_KC18NWIN, nullptr, key_tabs)
+  } else {
+    return hipErrorInvalidValue;
   }
 #undef BV_LAUNCH_QF
   return hipGetLastError();
@@ -1687,44 +1699,71 @@ hipError_t verify_gf(hipStream_t st, uint64_t n, uint64_t lo, uint64_t hi, const
   return hipGetLastError();
 }
 
-hipError_t verify_gq(hipStream_t st, uint64_t n, uint64_t lo, uint64_t hi, const uint32_t *item_key,
+// kw = 22 / 18: the context's cached geometry (KC / KC18).
+hipError_t verify_gq(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t hi, const uint32_t *item_key,
                      const uint32_t *r_be, const uint32_t *s_be, const uint8_t *pre, const uint8_t *kst,
                      const uint32_t *item_msg, const uint32_t *dig, const uint32_t *w, const uint32_t *g_table,
                      const uint64_t *key_tabs, uint8_t *status, uint64_t *bits) {
   if (hi <= lo) return hipSuccess;
-  if (lat_variant(n))
-    hipLaunchKernelGGL(k_verify_gq<true>, grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, r_be, s_be, pre,
-                       kst, item_msg, dig, w, g_table, key_tabs, status, bits);
-  else
-    hipLaunchKernelGGL(k_verify_gq<false>, grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, r_be, s_be, pre,
-                       kst, item_msg, dig, w, g_table, key_tabs, status, bits);
+  const bool lat = lat_variant(n);
+#define BV_LAUNCH_GQ(W, NWIN)                                                                                     \
+  if (lat)                                                                                                        \
+    hipLaunchKernelGGL((k_verify_gq<W, NWIN, true>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key,  \
+                       r_be, s_be, pre, kst, item_msg, dig, w, g_table, key_tabs, status, bits);                  \
+  else                                                                                                            \
+    hipLaunchKernelGGL((k_verify_gq<W, NWIN, false>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, \
+                       r_be, s_be, pre, kst, item_msg, dig, w, g_table, key_tabs, status, bits);
+  if (kw == BV_KCW) {
+    BV_LAUNCH_GQ(BV_KCW, BV_KCNWIN)
+  } else if (kw == BV_KC18W) {
+    BV_LAUNCH_GQ(BV_KC18W, BV_KC18NWIN)
+  } else {
+    return hipErrorInvalidValue;
+  }
+#undef BV_LAUNCH_GQ
   return hipGetLastError();
 }
 
-// Key-cache tables for n keys (decoded affine points kxy, statuses kst):
-// bases 2^(11 k) Q (k < 12), the 11-bit sub-tables into `sub`
-// (n * BV_KCSUB_U32 words), then every window's chord sums into
-// tabs[b] (BV_KCTABLE_U32 words each; k_verify_q forms the phi half).
-// `pscr`: n * kc_pscr_bytes() bytes.
-size_t kc_pscr_bytes() {
-  return (size_t)BV_KCNWIN * (BV_KCENT / BV_KCPAIR_ENT) * BV_KCPAIR_ENT * 32;
+// Key-cache tables for n keys (decoded affine points kxy, statuses kst) in
+// geometry kw (22: KC, 18: KC18): bases 2^(L k) Q (k < NSUB; L = 11 / 9,
+// NSUB = 12 / 16), the L-bit sub-tables into `sub` (n * kc_sub_bytes(kw)),
+// then every window's chord sums into tabs[b] (kc_table_bytes(kw) each;
+// the verify kernels form the phi half).  `pscr`: n * kc_pscr_bytes(kw)
+// bytes (32 per table slot: the prefix products of k_table_pair_kc).
+size_t kc_table_bytes(int kw) { return (size_t)(kw == BV_KC18W ? BV_KC18TABLE_U32 : BV_KCTABLE_U32) * 4; }
+size_t kc_sub_bytes(int kw) { return (size_t)(kw == BV_KC18W ? BV_KC18SUB_U32 : BV_KCSUB_U32) * 4; }
+size_t kc_pscr_bytes(int kw) {
+  return kw == BV_KC18W ? (size_t)BV_KC18NWIN * (BV_KC18ENT / BV_KCPAIR_ENT) * BV_KCPAIR_ENT * 32
+                        : (size_t)BV_KCNWIN * (BV_KCENT / BV_KCPAIR_ENT) * BV_KCPAIR_ENT * 32;
 }
-hipError_t build_kc(hipStream_t st, uint32_t n, const uint32_t *kxy, const uint8_t *kst, uint32_t *bases_jac,
-                    uint32_t *sub, uint32_t *pscr, const uint64_t *tabs) {
-  if (n == 0) return hipSuccess;
+template <int W, int L, int NWIN, int NSUB>
+static hipError_t build_kc_geom(hipStream_t st, uint32_t n, const uint32_t *kxy, const uint8_t *kst,
+                                uint32_t *bases_jac, uint32_t *sub, uint32_t *pscr, const uint64_t *tabs) {
+  static_assert(NSUB == 2 * NWIN && 2 * L == W, "two sub-tables per window");
+  static_assert((1u << (W - 1)) % BV_KCPAIR_ENT == 0, "whole k_table_pair_kc blocks per window");
+  constexpr uint32_t ENT = 1u << (W - 1);
   if (g_coop_bases)
-    hipLaunchKernelGGL(k_table_bases_coop, dim3(n), dim3(64), 0, st, n, kxy, kst, bases_jac, BV_KCL, BV_KCNSUB);
+    hipLaunchKernelGGL(k_table_bases_coop, dim3(n), dim3(64), 0, st, n, kxy, kst, bases_jac, L, NSUB);
   else
-    hipLaunchKernelGGL(k_table_bases<true>, grid1(n, 64), dim3(64), 0, st, n, kxy, kst, bases_jac, BV_KCL, BV_KCNSUB);
+    hipLaunchKernelGGL(k_table_bases<true>, grid1(n, 64), dim3(64), 0, st, n, kxy, kst, bases_jac, L, NSUB);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_table_fill<BV_KCL, BV_KCNSUB, false>), dim3(BV_KCNSUB * ((1u << BV_KCL) / 256u), n),
-                     dim3(256), 0, st, bases_jac, kst, sub);
+  hipLaunchKernelGGL((k_table_fill<L, NSUB, false>), dim3(NSUB * ((1u << L) / 256u), n), dim3(256), 0, st, bases_jac,
+                     kst, sub);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_table_pair_kc<BV_KCW, BV_KCL, BV_KCNWIN>),
-                     dim3(BV_KCNWIN * (BV_KCENT / BV_KCPAIR_ENT), n), dim3(256), 0, st, sub, kst, tabs, (uint4 *)pscr);
+  hipLaunchKernelGGL((k_table_pair_kc<W, L, NWIN>), dim3(NWIN * (ENT / BV_KCPAIR_ENT), n), dim3(256), 0, st, sub, kst,
+                     tabs, (uint4 *)pscr);
   return hipGetLastError();
+}
+hipError_t build_kc(hipStream_t st, int kw, uint32_t n, const uint32_t *kxy, const uint8_t *kst, uint32_t *bases_jac,
+                    uint32_t *sub, uint32_t *pscr, const uint64_t *tabs) {
+  if (n == 0) return hipSuccess;
+  if (kw == BV_KCW)
+    return build_kc_geom<BV_KCW, BV_KCL, BV_KCNWIN, BV_KCNSUB>(st, n, kxy, kst, bases_jac, sub, pscr, tabs);
+  if (kw == BV_KC18W)
+    return build_kc_geom<BV_KC18W, BV_KC18L, BV_KC18NWIN, BV_KC18NSUB>(st, n, kxy, kst, bases_jac, sub, pscr, tabs);
+  return hipErrorInvalidValue;
 }
 
 // (no timing events around a latency-bound launch: the kernel writes its

@@ -976,11 +976,12 @@ DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, cons
                           const uint32_t *s_be, const uint8_t *pre, const uint8_t *kstatus, const uint32_t *u12,
                           const uint32_t *key_table, const uint64_t *key_tabs, const uint32_t *rg) {
   constexpr bool SIGNED = W != BV_KW;
-  constexpr bool KC = W == BV_KCW;  // one stored half, phi(T) formed per lookup
+  constexpr bool KC = BV_W_IS_CACHED(W);  // one stored half, phi(T) formed per lookup
   constexpr uint64_t half =
       SIGNED ? ((uint64_t)NWIN * (1ull << (W - 1)) + 1) * BV_ENTRY_U32 : (uint64_t)NWIN * (1ull << W) * BV_ENTRY_U32;
   static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
-  static_assert(!KC || half == BV_KCHALF_U32, "KC geometry");
+  static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
+  static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
   fe r;
   const uint8_t st = classify_item(i, item_key, r_be, s_be, pre, kstatus, r);
   if (st != 0xFF) return st;
@@ -1019,9 +1020,12 @@ DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, co
                             const uint32_t *s_be, const uint8_t *pre, const uint8_t *kstatus, const uint32_t *w_in,
                             const uint32_t *key_table, const uint64_t *key_tabs, uint32_t *rq) {
   constexpr bool SIGNED = W != BV_KW;
-  constexpr bool KC = W == BV_KCW;
+  constexpr bool KC = BV_W_IS_CACHED(W);
   constexpr uint64_t half =
       SIGNED ? ((uint64_t)NWIN * (1ull << (W - 1)) + 1) * BV_ENTRY_U32 : (uint64_t)NWIN * (1ull << W) * BV_ENTRY_U32;
+  static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
+  static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
+  static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
   fe r;
   if (classify_item(i, item_key, r_be, s_be, pre, kstatus, r) != 0xFF) return;
   uint32_t k1[4], k2[4], signs;
@@ -1092,12 +1096,14 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
 // Key-cache path in ONE pass (k_verify_gq): R = u1 G + k1 T + k2 phi(T) with
 // the G table and the key's cached table, R_G kept in registers (no HBM
 // round trip of R_G / u12 between two kernels, no kernel boundary).  Same
-// decisions as verify_item_g followed by verify_item_q.
-template <bool LAT = false>
+// decisions as verify_item_g followed by verify_item_q.  <W, NWIN>: the
+// context's cached geometry (KC or KC18).
+template <int W, int NWIN, bool LAT = false>
 DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32_t *r_be, const uint32_t *s_be,
                               const uint8_t *pre, const uint8_t *kstatus, const uint32_t *item_msg,
                               const uint32_t *digest_words, const uint32_t *w_in, const uint32_t *g_table,
                               const uint64_t *key_tabs) {
+  static_assert(BV_W_IS_CACHED(W), "a cached geometry");
   fe r;
   const uint8_t st = classify_item(i, item_key, r_be, s_be, pre, kstatus, r);
   if (st != 0xFF) return st;
@@ -1119,7 +1125,7 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
   for (int h = 0; h < 2; h++) {
     uint32_t kk[4];
     glv_half<PARK>(kk, h, k1, k2, park);
-    key_table_add<BV_KCW, BV_KCNWIN, true, LAT>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1);
+    key_table_add<W, NWIN, true, LAT>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1);
   }
   fe_load_be_words(r, r_be + 8 * i);
   return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;

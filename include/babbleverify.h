@@ -72,16 +72,36 @@ extern "C" {
                              the cache budget (env BV_KEY_CACHE_GB, default
                              96), registered keys only for other registered
                              keys.  Malformed keys are never given a table.
-                             A batch whose valid keys without a table are at
-                             most 1 in 16 of its valid keys, carrying at most
-                             1 in 16 of its items, keeps the cache (their
-                             items are finished by the generic path after the
-                             cached ones); otherwise the batch takes the
-                             per-batch table path.  Off by default:
-                             tables are then rebuilt for every batch.          */
+                             A batch with one valid key that has no table
+                             takes the per-batch table path.  With env
+                             BV_KC_PARTIAL=1 (opt-in) a batch whose valid keys
+                             without a table are at most 1 in 16 of its valid
+                             keys, carrying at most 1 in 16 of its items,
+                             keeps the cache instead (their items are
+                             finished by the generic path after the cached
+                             ones).  Off by default: tables are then rebuilt
+                             for every batch.                                  */
 #define BV_F_K8 2u        /* per-batch tables: never use the 12-bit tables
                              (2.75 MiB per key); 8-bit only (512 KiB per key) */
-#define BV_F_KNOWN (BV_F_KEY_CACHE | BV_F_K8)
+#define BV_F_KC_COMPACT 4u /* with BV_F_KEY_CACHE only (alone: BV_E_ARGS): the
+                             context's cached tables use the compact KC18
+                             geometry, for validator sets past the 119 keys
+                             the 805 MB tables hold: 18-bit signed windows x 8
+                             over each GLV half, 67,108,928 bytes (67.1 MB)
+                             per valid key, so the default 96 GB budget holds
+                             1430 tables; 16 additions + 8 multiplies per item
+                             for u2 Q against 12 + 6.  A context has ONE
+                             cached geometry, fixed here.  Admission,
+                             registration, eviction and the budget work as
+                             above, per 67.1 MB table; bv_timing.key_path
+                             reports 18.  Small batches: the one-launch small
+                             path does not read KC18 tables, so batches of at
+                             most 256 items (env BV_SMALL_MAX) run it as for
+                             keys without a table (key_path 0), the 257-1024
+                             item extension for fully cached batches is off,
+                             and those batches take the bulk pipeline, which
+                             uses the tables (key_path 18).                    */
+#define BV_F_KNOWN (BV_F_KEY_CACHE | BV_F_K8 | BV_F_KC_COMPACT)
 
 typedef struct bv_ctx bv_ctx;
 
@@ -127,7 +147,8 @@ typedef struct {
                          last input copy enqueued                               */
   float ms_host_out;  /* host: results copied out after the device finished    */
   uint32_t key_path; /* 0: per-lane generic path; 8 / 12: per-batch K8 / K12
-                        key tables; 22: key-cache (KC) tables                   */
+                        key tables; 22: key-cache (KC) tables; 18: compact
+                        key-cache (KC18) tables, BV_F_KC_COMPACT                */
   uint32_t kc_hits;   /* batch keys found in the key cache                      */
   uint32_t kc_builds; /* key tables built into the cache by this call           */
   uint32_t kc_keys;   /* keys held by the cache after the call                  */
@@ -146,7 +167,8 @@ const char *bv_last_error(const bv_ctx *ctx);
  * registered valid keys that have none, before returning.  Registered tables
  * are never evicted for unregistered keys.  BV_E_ARGS on a ctx without the
  * cache or more than 4096 keys.  Cap: the budget holds floor(BV_KEY_CACHE_GB
- * / 0.805) tables (119 at the default 96 GB); past it, the first registered
+ * / 0.805) tables (119 at the default 96 GB), or with BV_F_KC_COMPACT
+ * floor(BV_KEY_CACHE_GB / 0.0671) (1430); past it, the first registered
  * keys in the caller's order that fit get tables and the rest none (their
  * batches take the per-batch path), still BV_OK.  bv_get_timing's kc_builds
  * / kc_keys report what was built and what the cache holds. */
