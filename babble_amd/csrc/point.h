@@ -274,7 +274,13 @@ DEV void gexz_set_ge(gexz &r, const fe &x, const fe &y) {
 // last addition before final_check), so the common path stops after X3 and
 // leaves Y and ZZZ stale: 3M + 2 sub fewer.  The identity, doubling and
 // P + (-P) cases are complete either way.
-DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false) {
+// EXC = false (BV_DEFER_EXC, verify_core.h): P is tested, and the doubling
+// and P + (-P) branches taken, only when `chk` (wave-uniform; the redo of a
+// flagged item).  Without it a step with P == 0 leaves ZZ3 = ZZ1 P^2 == 0
+// (and finite garbage elsewhere), which the caller tests once after its last
+// addition.
+template <bool EXC = true>
+DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false) {
   if (inf) {
     gexz_set_ge(r, x2, y2);
     inf = false;
@@ -285,7 +291,7 @@ DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_onl
   fe_sub(P, P, r.X);         // P = U2 - X1
   fe_mul(R, y2, r.ZZZ);      // S2
   fe_sub(R, R, r.Y);         // R = S2 - Y1
-  if (fe_is_zero(P)) {
+  if ((EXC || chk) && fe_is_zero(P)) {
     if (fe_is_zero(R)) {
       gexz d;
       gexz_double(d, r);
@@ -307,10 +313,20 @@ DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_onl
   if (xz_only) return;
   // Y3 = R (Q - X3) - Y1 PPP, ZZZ3 = ZZZ1 PPP
   fe_sub(t, Q, r.X);
+#if BV_FUSED_Y3
+  // as R (Q - X3) + (-Y1) PPP: one Comba pass and one fold (fe_mul2add)
+  // instead of two products, two folds and a subtraction.  The weak
+  // negation (a 13-VALU fe_sub from 0) costs less than the fold it removes;
+  // Y3 is the same residue, so the accumulator is the same point.
+  fe_neg(Q, r.Y);  // Q is dead
+  fe_mul(r.ZZZ, r.ZZZ, PPP);
+  fe_mul2add(r.Y, R, t, Q, PPP);
+#else
   fe_mul(t, R, t);
   fe_mul(r.ZZZ, r.ZZZ, PPP);
   fe_mul(PPP, r.Y, PPP);
   fe_sub(r.Y, t, PPP);
+#endif
 }
 
 // The same for latency-bound launches: four dependent levels of
@@ -488,22 +504,22 @@ DEV void gexz_from_gej(gexz &r, const gej &a) {
   fe_mul(r.ZZZ, r.ZZ, a.Z);
 }
 
-template <bool LAT>
-DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false) {
+template <bool LAT, bool EXC = true>
+DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false) {
   if (LAT) gexz_add_ge_lat(r, inf, x2, y2);  // latency variants always form the whole sum
-  else gexz_add_ge(r, inf, x2, y2, xz_only);
+  else gexz_add_ge<EXC>(r, inf, x2, y2, xz_only, chk);
 }
 
 // r += (x2, y2) for r AFFINE (ZZ = ZZZ = 1, not the identity: the first
 // table entry of a sum), mmadd-2008-s: 4M + 2S — the products by ZZ1 and
 // ZZZ1 of the general step drop out (U2 = x2, S2 = y2, ZZ3 = PP, ZZZ3 =
-// PPP).  Same exceptional cases as gexz_add_ge.
-template <bool LAT>
-DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2) {
+// PPP).  Same exceptional cases as gexz_add_ge (and the same EXC / chk).
+template <bool LAT, bool EXC = true>
+DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2, bool chk = false) {
   fe P, R, PP, RR, PPP, Q, t, u, v;
   fe_sub(P, x2, r.X);
   fe_sub(R, y2, r.Y);
-  if (fe_is_zero(P)) {
+  if ((EXC || chk) && fe_is_zero(P)) {
     if (fe_is_zero(R)) {
       gexz d;
       gexz_double(d, r);
@@ -538,6 +554,11 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2) {
   } else
 #endif
   {
+    if (BV_FUSED_Y3 && !LAT) {  // the throughput form: see gexz_add_ge
+      fe_neg(v, r.Y);
+      fe_mul2add(r.Y, R, u, v, PPP);
+      return;
+    }
     fe_mul(t, R, u);
     fe_mul(v, r.Y, PPP);
   }
@@ -553,12 +574,14 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2) {
 // variants at 2-3 waves per SIMD run 10-15 % slower; this per-lane form
 // stays.
 // `xz_only`: see gexz_add_ge (XYZZ throughput form only; ignored elsewhere).
-template <bool LAT>
-DEV void pt_add_ge_step(gexz &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false) {
-  if (take) pt_add_ge<LAT>(r, inf, x2, y2, xz_only);
+template <bool LAT, bool EXC = true>
+DEV void pt_add_ge_step(gexz &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false,
+                        bool chk = false) {
+  if (take) pt_add_ge<LAT, EXC>(r, inf, x2, y2, xz_only, chk);
 }
-template <bool LAT>
-DEV void pt_add_ge_step(gej &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false) {
+template <bool LAT, bool EXC = true>
+DEV void pt_add_ge_step(gej &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false,
+                        bool chk = false) {
   if (take) gej_add_ge_sel<LAT>(r, inf, x2, y2);
 }
 template <bool LAT>

@@ -616,6 +616,60 @@ DEV bool final_check(const gexz &R, bool inf, const fe &r) {
 #endif
 #define BV_STAGE_LANES 256  // threads per block of every throughput verify kernel
 
+// ---------------------------------------------------------------------------
+// One exception test per item (BV_DEFER_EXC, compile-time; 0 keeps the test
+// of P in every addition).  With 1 the pipelined throughput loops below add
+// with gexz_add_ge<false>: no fe_is_zero(P), no doubling or P + (-P) branch.
+// Lemma: ZZ_final == 0 (mod p)  <=>  some step of the item had P == 0.
+//   Every non-identity step multiplies ZZ by P^2 (ZZ3 = ZZ1 P^2, the affine
+//   step: ZZ3 = P^2); F_p has no zero divisors; and every chain starts from
+//   ZZ = 1 (the first entry taken by an identity accumulator) or from a
+//   stored partial sum that passed this same test before it was stored.
+// A step with P == 0 is exactly a doubling (R == 0 as well) or P + (-P): the
+// lane's later values are finite garbage (table addresses come from the
+// digits, never from the accumulator).  The one test after the item's last
+// loop sends a flagged lane round again, under a wave-uniform "any lane
+// flagged" branch: it reloads the item from memory and runs the same loops
+// with `chk` set, which is the per-step-checked code BV_DEFER_EXC = 0 runs.
+// `chk` is uniform (every lane still in the loop has it set), one SGPR.
+// The `inf` flag needs no test of its own: in the unchecked chain it only
+// goes from true to false (the identity taking an entry, which is exact);
+// the only way a checked chain sets it mid-chain is P + (-P), a P == 0
+// step, so the item is flagged and the second pass replays that step.
+// ---------------------------------------------------------------------------
+// Default 0: measured on MI355X the deferred form loses (DESIGN.md section 4,
+// round 9: the second pass's live ranges cost the throughput kernels spills
+// inside the addition loop and k_verify_g its fourth wave per SIMD); the
+// knob, its tests and the A/B stay.
+#ifndef BV_DEFER_EXC
+#define BV_DEFER_EXC 0
+#endif
+#if !defined(__HIP_DEVICE_COMPILE__)
+// host builds (tests): items that took the second, checked pass
+inline uint64_t &bv_defer_redo_count() {
+  static uint64_t n = 0;
+  return n;
+}
+#endif
+// true for the whole wave when any of its lanes must redo its item
+DEV bool defer_any_flagged(bool bad) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ballot(bad) != 0;
+#else
+  if (bad) __atomic_fetch_add(&bv_defer_redo_count(), 1, __ATOMIC_RELAXED);
+  return bad;
+#endif
+}
+DEV bool defer_flagged(const gexz &R, bool inf) { return !inf && fe_is_zero(R.ZZ); }
+// the pass flag as a scalar (it is uniform by construction)
+DEV bool defer_uniform(bool chk) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(chk ? 1 : 0) != 0;
+#else
+  return chk;
+#endif
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ uint4 *entry_stage_slots() {
   __shared__ uint4 slots[4 * BV_STAGE_LANES];
@@ -730,10 +784,15 @@ DEV uint32_t next_digit(uint32_t *u, uint32_t &carry, bool &dneg) {
 // (gexz_add_ge_aff) — 4 multiplies fewer per item.
 // FINAL: only X and ZZ of the sum are read afterwards (final_check), so the
 // top window's addition is the trimmed one (gexz_add_ge xz_only).
-template <int W, int NWIN, bool LAT = false, class PT = gej, bool FROM_INF = false, bool FINAL = false>
-DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8]) {
+// DEFER (pipelined XYZZ loop only): the additions test P only when `chk`
+// (BV_DEFER_EXC above); the caller tests ZZ after its last loop.
+template <int W, int NWIN, bool LAT = false, class PT = gej, bool FROM_INF = false, bool FINAL = false,
+          bool DEFER = false>
+DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool chk = false) {
   constexpr uint32_t ENT = 1u << (W - 1);
   static_assert(W * NWIN >= 257 && W < 32, "signed G windows must absorb the last carry");
+  static_assert(!DEFER || ((BV_LOOKUP_PIPE & 1) && !LAT && std::is_same<PT, gexz>::value),
+                "deferred additions only in the pipelined throughput loop");
   uint32_t carry = 0;
   if constexpr ((BV_LOOKUP_PIPE & 1) && !LAT && std::is_same<PT, gexz>::value) {
     entry_stage stage;
@@ -753,11 +812,11 @@ DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8]) {
       fe_cneg_canon(y, nj);
       if constexpr (FROM_INF) {
         if (j == 1 && !inf) {  // R = window 0's entry (affine)
-          if (dj != 0) gexz_add_ge_aff<LAT>(R, inf, x, y);
+          if (dj != 0) gexz_add_ge_aff<LAT, !DEFER>(R, inf, x, y, chk);
           continue;
         }
       }
-      pt_add_ge_step<LAT>(R, inf, x, y, dj != 0, FINAL && j == NWIN - 1);
+      pt_add_ge_step<LAT, !DEFER>(R, inf, x, y, dj != 0, FINAL && j == NWIN - 1, chk);
     }
     return;
   }
@@ -850,35 +909,53 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
                        const uint8_t *pre, const uint8_t *kstatus, const uint32_t *item_msg,
                        const uint32_t *digest_words, const uint32_t *w_in, uint32_t *u12, const uint32_t *g_table,
                        uint32_t *rg) {
+  constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 1) != 0 && !LAT;
   fe r;
   if (classify_item(i, item_key, r_be, s_be, pre, kstatus, r) != 0xFF) return;
-  uint32_t u[8];
-  if (SPLIT) {
-    sc w, e, a;
-    const uint4 *q = (const uint4 *)(w_in + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-    w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-    sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
-    sc_mont(a, e, w);  // e * s^-1 mod N
+  for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
+    chk = defer_uniform(chk);
+    uint32_t u[8];
+    if (SPLIT) {
+      sc w, e, a;
+      const uint4 *q = (const uint4 *)(w_in + 8 * i);
+      const uint4 x = q[0], y = q[1];
+      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
+      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
+      sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
+      sc_mont(a, e, w);  // e * s^-1 mod N
 #pragma unroll
-    for (int k = 0; k < 8; k++) u[k] = a.v[k];
-  } else {
-    uint32_t k1[4], k2[4], signs;
-    item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
-    uint4 *q = (uint4 *)(u12 + (uint64_t)BV_U_STRIDE * i);
-    q[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
-    q[1] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
-    q[2] = make_uint4(signs, 0u, 0u, 0u);
+      for (int k = 0; k < 8; k++) u[k] = a.v[k];
+    } else {
+      uint32_t k1[4], k2[4], signs;
+      item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
+      uint4 *q = (uint4 *)(u12 + (uint64_t)BV_U_STRIDE * i);
+      q[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
+      q[1] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
+      q[2] = make_uint4(signs, 0u, 0u, 0u);
+    }
+    gexz R;
+    bool inf = true;
+    fe_set(R.X, 0);
+    fe_set(R.Y, 0);
+    fe_set(R.ZZ, 0);
+    fe_set(R.ZZZ, 0);
+    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER>(R, inf, g_table, u, chk);
+    if constexpr (DEFER) {
+      // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC).  On this
+      // chain it cannot happen (the partial sums
+      // of the signed digits are smaller than the next entry's scalar and the
+      // total is u1 in (0, N)); the test stays, so that the stored R_G, from
+      // which k_verify_q's chain starts, provably has ZZ != 0.
+      if (!chk) {
+        const bool bad = defer_flagged(R, inf);
+        if (defer_any_flagged(bad)) {
+          if (bad) continue;
+        }
+      }
+    }
+    rg_store(rg, n, i, R, inf);
+    return;
   }
-  gexz R;
-  bool inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.ZZ, 0);
-  fe_set(R.ZZZ, 0);
-  g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true>(R, inf, g_table, u);
-  rg_store(rg, n, i, R, inf);
 }
 
 // R += sum_j T[j][digit_j(k)] over a 128-bit GLV half k (4 limbs; consumed:
@@ -895,11 +972,14 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
 // entries and negating back gives, without the two field negations.
 // `last` (uniform; XYZZ throughput form): only X and ZZ of the sum are read
 // afterwards, so the top window's addition is the trimmed one.
-template <int W, int NWIN, bool SIGNED, bool LAT = false, class PT = gexz>
+// DEFER / chk: as g_table_add.
+template <int W, int NWIN, bool SIGNED, bool LAT = false, class PT = gexz, bool DEFER = false>
 DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], bool neg, bool phi = false,
-                       bool from_inf = false, bool last = false) {
+                       bool from_inf = false, bool last = false, bool chk = false) {
   constexpr uint32_t ENT = SIGNED ? (1u << (W - 1)) : (1u << W);
   static_assert(!SIGNED || W * NWIN >= 129, "signed windows must absorb the last carry");
+  static_assert(!DEFER || ((BV_LOOKUP_PIPE & 2) && !LAT && std::is_same<PT, gexz>::value),
+                "deferred additions only in the pipelined throughput loop");
   uint32_t carry = 0;
   if constexpr ((BV_LOOKUP_PIPE & 2) && !LAT && std::is_same<PT, gexz>::value) {
     entry_stage stage;
@@ -923,10 +1003,10 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
       }
       fe_cneg_canon(y, nj);
       if (from_inf && j == 1 && !inf) {  // R = window 0's entry (affine)
-        if (dj != 0) gexz_add_ge_aff<LAT>(R, inf, x, y);
+        if (dj != 0) gexz_add_ge_aff<LAT, !DEFER>(R, inf, x, y, chk);
         continue;
       }
-      pt_add_ge_step<LAT>(R, inf, x, y, dj != 0, last && j == NWIN - 1);
+      pt_add_ge_step<LAT, !DEFER>(R, inf, x, y, dj != 0, last && j == NWIN - 1, chk);
     }
     return;
   }
@@ -982,31 +1062,47 @@ DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, cons
   static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
   static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
   static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
+  constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 2) != 0 && !LAT;
   fe r;
   const uint8_t st = classify_item(i, item_key, r_be, s_be, pre, kstatus, r);
   if (st != 0xFF) return st;
-  uint32_t k1[4], k2[4], signs;
-  load_k(k1, k2, signs, u12, i);
-  gexz R;
-  bool inf;
-  rg_load(rg, n, i, R, inf);
   const uint32_t *tab = key_tabs ? (const uint32_t *)key_tabs[item_key[i]]
                                  : key_table + (uint64_t)item_key[i] * (KC ? 1 : 2) * half;
   if (!tab) return BV_DEFERRED;  // key cache, partial batch: no table for this key
-  // One loop body for both GLV halves (one inlined copy of the point
-  // addition: smaller code, fewer live registers than two calls).
-  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-  lane_park park;
-  if (PARK) park.put(k2);
+  for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
+    chk = defer_uniform(chk);
+    uint32_t k1[4], k2[4], signs;
+    load_k(k1, k2, signs, u12, i);
+    gexz R;
+    bool inf;
+    rg_load(rg, n, i, R, inf);
+    // One loop body for both GLV halves (one inlined copy of the point
+    // addition: smaller code, fewer live registers than two calls).
+    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+    lane_park park;
+    if (PARK) park.put(k2);
 #pragma unroll 1
-  for (int h = 0; h < 2; h++) {
-    uint32_t kk[4];
-    glv_half<PARK>(kk, h, k1, k2, park);
-    key_table_add<W, NWIN, SIGNED, LAT>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u, KC && h, false,
-                                        h == 1);
+    for (int h = 0; h < 2; h++) {
+      uint32_t kk[4];
+      glv_half<PARK>(kk, h, k1, k2, park);
+      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u,
+                                                       KC && h, false, h == 1, chk);
+    }
+    if constexpr (DEFER) {
+      // ZZ == 0 <=> some step of either half had P == 0 (the lemma at
+      // BV_DEFER_EXC; R_G entered with ZZ != 0: k_verify_g tested it).  The
+      // flagged item starts again from R_G and u12 in memory, every step
+      // checked.
+      if (!chk) {
+        const bool bad = defer_flagged(R, inf);
+        if (defer_any_flagged(bad)) {
+          if (bad) continue;
+        }
+      }
+    }
+    fe_load_be_words(r, r_be + 8 * i);  // reloaded: not kept live through the loop
+    return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
-  fe_load_be_words(r, r_be + 8 * i);  // reloaded: not kept live through the loop
-  return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
 }
 
 // Key part first, for host entries whose messages are still crossing PCIe:
@@ -1026,42 +1122,59 @@ DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, co
   static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
   static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
   static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
+  constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 2) != 0 && !LAT;
   fe r;
   if (classify_item(i, item_key, r_be, s_be, pre, kstatus, r) != 0xFF) return;
-  uint32_t k1[4], k2[4], signs;
-  {
-    sc w, rs, b;
-    const uint4 *q = (const uint4 *)(w_in + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-    w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-    sc_load_be_words(rs, r_be + 8 * i);
-    sc_mont(b, rs, w);  // r * s^-1 mod N
-    glv_split(k1, k2, signs, b);
-  }
-  gexz R;
-  bool inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.ZZ, 0);
-  fe_set(R.ZZZ, 0);
   const uint32_t *tab = key_tabs ? (const uint32_t *)key_tabs[item_key[i]]
                                  : key_table + (uint64_t)item_key[i] * (KC ? 1 : 2) * half;
   if (!tab) {  // key cache, partial batch: k_verify_gf leaves the item BV_DEFERRED
     rq[(uint64_t)32 * n + i] = 2u;
     return;
   }
-  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-  lane_park park;
-  if (PARK) park.put(k2);
+  for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
+    chk = defer_uniform(chk);
+    uint32_t k1[4], k2[4], signs;
+    {
+      sc w, rs, b;
+      const uint4 *q = (const uint4 *)(w_in + 8 * i);
+      const uint4 x = q[0], y = q[1];
+      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
+      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
+      sc_load_be_words(rs, r_be + 8 * i);
+      sc_mont(b, rs, w);  // r * s^-1 mod N
+      glv_split(k1, k2, signs, b);
+    }
+    gexz R;
+    bool inf = true;
+    fe_set(R.X, 0);
+    fe_set(R.Y, 0);
+    fe_set(R.ZZ, 0);
+    fe_set(R.ZZZ, 0);
+    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+    lane_park park;
+    if (PARK) park.put(k2);
 #pragma unroll 1
-  for (int h = 0; h < 2; h++) {
-    uint32_t kk[4];
-    glv_half<PARK>(kk, h, k1, k2, park);
-    key_table_add<W, NWIN, SIGNED, LAT>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u, KC && h,
-                                        h == 0);
+    for (int h = 0; h < 2; h++) {
+      uint32_t kk[4];
+      glv_half<PARK>(kk, h, k1, k2, park);
+      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u,
+                                                       KC && h, h == 0, false, chk);
+    }
+    if constexpr (DEFER) {
+      // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC; the
+      // chain starts from the identity).  The flagged item starts again from
+      // w_in, every step checked, so the stored R_Q has ZZ != 0 when
+      // k_verify_gf continues from it.
+      if (!chk) {
+        const bool bad = defer_flagged(R, inf);
+        if (defer_any_flagged(bad)) {
+          if (bad) continue;
+        }
+      }
+    }
+    rg_store(rq, n, i, R, inf);
+    return;
   }
-  rg_store(rq, n, i, R, inf);
 }
 
 template <bool LAT = false>
@@ -1073,24 +1186,40 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
   const uint8_t st = classify_item(i, item_key, r_be, s_be, pre, kstatus, r);
   if (st != 0xFF) return st;
   if (rq[(uint64_t)32 * n + i] == 2u) return BV_DEFERRED;  // no key table (k_verify_qf)
-  uint32_t u[8];
-  {
-    sc w, e, a;
-    const uint4 *q = (const uint4 *)(w_in + 8 * i);
-    const uint4 x = q[0], y = q[1];
-    w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-    w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-    sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
-    sc_mont(a, e, w);  // e * s^-1 mod N  (e < 2^256 = R, w < N)
+  constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 1) != 0 && !LAT;
+  for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
+    chk = defer_uniform(chk);
+    uint32_t u[8];
+    {
+      sc w, e, a;
+      const uint4 *q = (const uint4 *)(w_in + 8 * i);
+      const uint4 x = q[0], y = q[1];
+      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
+      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
+      sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
+      sc_mont(a, e, w);  // e * s^-1 mod N  (e < 2^256 = R, w < N)
 #pragma unroll
-    for (int k = 0; k < 8; k++) u[k] = a.v[k];
+      for (int k = 0; k < 8; k++) u[k] = a.v[k];
+    }
+    gexz R;
+    bool inf;
+    rg_load(rq, n, i, R, inf);
+    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, false, true, DEFER>(R, inf, g_table, u, chk);
+    if constexpr (DEFER) {
+      // ZZ == 0 <=> some G step had P == 0 (the lemma at BV_DEFER_EXC; R_Q
+      // entered with ZZ != 0: k_verify_qf tested it).  G entries added to
+      // R_Q can meet R_Q itself or its opposite, so here the test does fire:
+      // the flagged item starts again from R_Q in memory, every step checked.
+      if (!chk) {
+        const bool bad = defer_flagged(R, inf);
+        if (defer_any_flagged(bad)) {
+          if (bad) continue;
+        }
+      }
+    }
+    fe_load_be_words(r, r_be + 8 * i);
+    return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
-  gexz R;
-  bool inf;
-  rg_load(rq, n, i, R, inf);
-  g_table_add<BV_GW, BV_GNWIN, LAT, gexz, false, true>(R, inf, g_table, u);
-  fe_load_be_words(r, r_be + 8 * i);
-  return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
 }
 
 // Key-cache path in ONE pass (k_verify_gq): R = u1 G + k1 T + k2 phi(T) with
@@ -1109,26 +1238,42 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
   if (st != 0xFF) return st;
   const uint32_t *tab = (const uint32_t *)key_tabs[item_key[i]];
   if (!tab) return BV_DEFERRED;  // partial batch: no table for this key
-  uint32_t u[8], k1[4], k2[4], signs;
-  item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
-  gexz R;
-  bool inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.ZZ, 0);
-  fe_set(R.ZZZ, 0);
-  g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true>(R, inf, g_table, u);
-  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-  lane_park park;
-  if (PARK) park.put(k2);
+  // deferred only when both loops are the pipelined ones: one test for the item
+  constexpr bool DEFER = BV_DEFER_EXC != 0 && BV_LOOKUP_PIPE == 3 && !LAT;
+  for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
+    chk = defer_uniform(chk);
+    uint32_t u[8], k1[4], k2[4], signs;
+    item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
+    gexz R;
+    bool inf = true;
+    fe_set(R.X, 0);
+    fe_set(R.Y, 0);
+    fe_set(R.ZZ, 0);
+    fe_set(R.ZZZ, 0);
+    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER>(R, inf, g_table, u, chk);
+    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+    lane_park park;
+    if (PARK) park.put(k2);
 #pragma unroll 1
-  for (int h = 0; h < 2; h++) {
-    uint32_t kk[4];
-    glv_half<PARK>(kk, h, k1, k2, park);
-    key_table_add<W, NWIN, true, LAT>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1);
+    for (int h = 0; h < 2; h++) {
+      uint32_t kk[4];
+      glv_half<PARK>(kk, h, k1, k2, park);
+      key_table_add<W, NWIN, true, LAT, gexz, DEFER>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1, chk);
+    }
+    if constexpr (DEFER) {
+      // ZZ == 0 <=> some step of the G chain or of either half had P == 0
+      // (the lemma at BV_DEFER_EXC; the item's one chain starts from the
+      // identity).  The flagged item starts again, every step checked.
+      if (!chk) {
+        const bool bad = defer_flagged(R, inf);
+        if (defer_any_flagged(bad)) {
+          if (bad) continue;
+        }
+      }
+    }
+    fe_load_be_words(r, r_be + 8 * i);
+    return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
-  fe_load_be_words(r, r_be + 8 * i);
-  return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
 }
 
 // One signature item without a key table: k1 Q + k2 phi(Q) by a joint

@@ -61,6 +61,10 @@ NCARRY = 10        # SGPR lane-mask pairs of fe_mul / fe_sqr (%[c0..9])
 OPS = {
     "mad": ((1, 2), (3, 4, 5), ()),        # d64, cy | a, b, c64
     "addc": ((1, 2), (3, 4, 5), (5,)),     # d, cy | a, b, cin
+    # the same instructions where the program claims a zero carry-out: the
+    # interpreter asserts it (fe_mul2add's bounds)
+    "mad_nc": ((1, 2), (3, 4, 5), ()),
+    "addc_nc": ((1, 2), (3, 4, 5), (5,)),
     "add_co": ((1, 2), (3, 4), ()),
     "subb": ((1, 2), (3, 4, 5), (5,)),
     "sub_co": ((1, 2), (3, 4), ()),
@@ -341,6 +345,7 @@ class Machine:
         self._run(g, force_slow)
         if g.slow is not None:
             mask, blk = g.slow
+            self.hits[blk.name] = self.hits.get(blk.name, 0) + bool(self.get(mask))
             if force_slow or self.get(mask):
                 self.run(blk, force_slow)
 
@@ -351,20 +356,23 @@ class Machine:
                 continue
             if op == "slow":
                 self.hits[g.name] = self.hits.get(g.name, 0) + bool(self.get(x[1]))
+                self.hits[x[2].name] = self.hits.get(x[2].name, 0) + bool(self.get(x[1]))  # per block
                 if force_slow or self.get(x[1]):
                     self.run(x[2], force_slow)
                 continue
             if op == "sor":
                 self.put(x[1], 1 if (self.get(x[2]) or self.get(x[3])) else 0)
                 continue
-            if op == "mad":
+            if op in ("mad", "mad_nc"):
                 s = self.get(x[3]) * self.get(x[4]) + self.get(x[5])
                 self.put(x[1], s & M64)
                 self.put(x[2], s >> 64)
-            elif op in ("addc", "add_co"):
-                s = self.get(x[3]) + self.get(x[4]) + (self.get(x[5]) if op == "addc" else 0)
+                assert op == "mad" or s >> 64 == 0, (g.name, x)
+            elif op in ("addc", "add_co", "addc_nc"):
+                s = self.get(x[3]) + self.get(x[4]) + (self.get(x[5]) if op != "add_co" else 0)
                 self.put(x[1], s & M32)
                 self.put(x[2], s >> 32)
+                assert op != "addc_nc" or s >> 32 == 0, (g.name, x)
             elif op in ("subb", "sub_co"):
                 s = self.get(x[3]) - self.get(x[4]) - (self.get(x[5]) if op == "subb" else 0)
                 self.put(x[1], s & M32)
@@ -532,6 +540,138 @@ def _fold(g: Prog, base: int, R, Pl, Ph, PP) -> Prog:
     cG = CY[2]
     t.add_co(R[0], cG, R[0], T3)
     t.addc(R[1], cG, R[1], T1, cG)
+    t.addc(R[2], cG, R[2], 0, cG)
+    g.slow = (cF, t)
+    return g
+
+
+def _mul2_product(g: Prog, base: int, fast: bool):
+    """Columns of a b + x y: both products accumulate into the same 15
+    column pairs (gen_mul's scheme, up to 16 products a column).  Differences
+    from one product: column 0 holds two products, so its second one is
+    counted; column 1's addend then carries a count, so its first product is
+    checked like every other; and the sum is below 2^513, so column 14 is
+    counted too: its count w_16 (0 or 1) goes to v[base + 31]."""
+    A = [f"%[a{i}]" for i in range(8)]
+    B = [f"%[b{i}]" for i in range(8)]
+    X = [f"%[x{i}]" for i in range(8)]
+    Y = [f"%[y{i}]" for i in range(8)]
+    Pl = [v(base + 2 * k) for k in range(15)]
+    Ph = [v(base + 2 * k + 1) for k in range(15)]
+    PP = [pair(x) for x in Pl]
+    W16 = v(base + 31)
+    first = True
+    for k in range(15):
+        terms = [(A[i], B[k - i]) for i in range(8) if 0 <= k - i < 8]
+        terms += [(X[i], Y[k - i]) for i in range(8) if 0 <= k - i < 8]
+        src = 0 if k == 0 else PP[k]
+        c2 = Ph[k + 1] if k < 14 else W16
+        wrote = False  # c2 has been written in this column
+        for j, (p, q) in enumerate(terms):
+            cy = CY[j % 3]
+            can_carry = not (k == 0 and j == 0)  # 0 + a b < 2^64
+            flag_only = fast and can_carry and j == 0
+            direct = flag_only and first
+            g.mad(PP[k], RARE if direct else cy, p, q, src)
+            src = PP[k]
+            if not can_carry:
+                continue
+            if flag_only:
+                if not direct:
+                    g.sor(RARE, cy, RARE)
+                first = False
+            else:
+                g.addc(c2, cy, c2 if wrote else 0, 0, cy)
+                wrote = True
+        assert wrote
+        if k < 14:
+            g.mov(Pl[k + 1], Ph[k])
+        if k >= 8:
+            g.mov(Ph[k - 8], Pl[k])  # P_(k-8) = {w_(k-8), w_k} for the fold
+    g.mov(Ph[7], Ph[14])             # P_7 = {w_7, w_15}
+    return Pl, Ph, PP, W16
+
+
+def gen_mul2add(base: int = MUL_BASE) -> Prog:
+    """r = a b + x y mod p, weakly reduced: ONE Comba pass over both
+    products (128 mads into the same columns) and ONE fold, against two
+    products, two folds and an add/sub.  Operands %[a0..7], %[b0..7],
+    %[x0..7], %[y0..7] -> %[r0..7]; temporaries and carries as fe_mul.
+
+    The sum is a 513-bit value w_0..w_16 (w_16 in {0, 1}).  The fold is
+    fe_mul's with one more limb: Y_8 = w_16 (2^32 + 977) joins the carry
+    chain, so the part above 2^256 is R_8 + 2^32 R_9 with R_9 a NUMBER in
+    0..2 (fe_mul's c9 is one bit: there the value folded is below
+    2^256 (2^32 + 978); here below 2^256 (2^33 + 1955), so R_9 = 1 leaves
+    R_8 arbitrary and the second fold adds with full carries):
+        (R_8 + 2^32 R_9) (2^32 + 977)
+            = 977 R_8 + 2^32 R_8          (one mad, carry-out cE at 2^64)
+            + 2^32 (977 R_9) + 2^64 R_9   (one mad into limbs 1..2)
+    below 2^67, into limbs 0..2; the rare tail is fe_mul's."""
+    g = Prog("fe_mul2add")
+    R = [f"%[r{i}]" for i in range(8)]
+    Pl, Ph, PP, W16 = _mul2_product(g, base, FAST_FIRST)
+    if FAST_FIRST:
+        blk = Prog("fe_mul2add_recount")
+        _mul2_product(blk, base, False)
+        g.slow_block(RARE, blk)
+    T0, T2, T3 = v(base + 30), v(base + 32), v(base + 33)
+    K977 = T2
+    YC = [f"%[c{i}]" for i in range(8)]
+    CANY, cR = "%[c8]", "%[c9]"
+    H = [Pl[i + 8] for i in range(7)] + [Ph[14]]
+    R8, R9 = Ph[8], W16              # limbs 8 and 9 of the folded value
+    E, D = PP[8], PP[9]              # free once the fold's mads have read w_8, w_9
+
+    g.mov(K977, 977)
+    g.mad(PP[0], YC[0], H[0], K977, PP[0])
+    g.mad(PP[1], YC[1], H[1], K977, PP[1])
+    g.sor(CANY, YC[0], YC[1])
+    g.add_co(R[1], cR, Pl[1], Ph[0])
+    for i in range(2, 8):
+        g.mad(PP[i], YC[i], H[i], K977, PP[i])
+        g.sor(CANY, CANY, YC[i])
+        g.addc(R[i], cR, Pl[i], Ph[i - 1], cR)
+    g.mul24(T0, W16, K977)                  # Y_8 = {977 w_16, w_16}: no carry-out
+    g.addc(R8, cR, Ph[7], T0, cR)
+    g.emit("addc_nc", R9, cR, W16, 0, cR)   # R_9 <= 2
+
+    # ---- rare: y_i -> limb i + 2, limbs 2..9 as one chain (R_9 is a number,
+    # so y_7 and the carry out of limb 8 are simply added) ----
+    s = Prog(g.name + "_ycarry")
+    cS = CANY
+    limbs = [R[2], R[3], R[4], R[5], R[6], R[7], R8, R9]
+    XT = [Ph[10], Ph[11]]                   # free since the product phase
+    for i in range(8):
+        x = XT[i % 2]
+        s.cnd(x, 0, 1, YC[i])
+        if i == 0:
+            s.add_co(limbs[0], cS, limbs[0], x)
+        else:
+            s.emit("addc_nc" if i == 7 else "addc", limbs[i], cS, limbs[i], x, cS)  # R_9 stays <= 2
+    g.slow_block(CANY, s)
+
+    # ---- second fold: (R_8 + 2^32 R_9)(2^32 + 977) into limbs 0..2 ----
+    cE = CY[0]
+    g.mov(Pl[8], 0)
+    g.mad(E, cE, R8, K977, E)               # {limb 0, limb 1 part}, cE at 2^64
+    g.mov(Pl[9], Ph[8])
+    g.cnd(Ph[9], 0, 1, cE)
+    g.add(Ph[9], Ph[9], R9)
+    g.emit("mad_nc", D, CY[2], R9, K977, D)  # limbs 1..2 (+ 977 R_9 at limb 1): below 2^35
+    cF = CY[1]
+    g.add_co(R[0], cF, Pl[0], Pl[8])
+    g.addc(R[1], cF, R[1], Pl[9], cF)
+    g.addc(R[2], cF, R[2], Ph[9], cF)
+    # ---- rare tail, as fe_mul's: the value that wrapped is below 2^67 ----
+    t = Prog(g.name + "_tail")
+    for i in range(3, 8):
+        t.addc(R[i], cF, R[i], 0, cF)
+    t.cnd(T3, 0, T2, cF)
+    t.cnd(T0, 0, 1, cF)
+    cG = CY[2]
+    t.add_co(R[0], cG, R[0], T3)
+    t.addc(R[1], cG, R[1], T0, cG)
     t.addc(R[2], cG, R[2], 0, cG)
     g.slow = (cF, t)
     return g
@@ -742,7 +882,8 @@ def gen_mont(base: int = MONT_BASE) -> Prog:
     return g
 
 
-PROGRAMS = {"fe_mul": gen_mul, "fe_sqr": gen_sqr, "fe_add": gen_add, "fe_sub": gen_sub, "sc_mont": gen_mont}
+PROGRAMS = {"fe_mul": gen_mul, "fe_sqr": gen_sqr, "fe_add": gen_add, "fe_sub": gen_sub, "sc_mont": gen_mont,
+            "fe_mul2add": gen_mul2add}
 
 
 # ---------------------------------------------------------------------------
@@ -848,9 +989,9 @@ def asm_line(x) -> str:
     op = x[0]
     if op == "nop":
         return "s_nop 0"
-    if op == "mad":
+    if op in ("mad", "mad_nc"):
         return f"v_mad_u64_u32 {fmt(x[1])}, {fmt(x[2])}, {fmt(x[3])}, {fmt(x[4])}, {fmt(x[5])}"
-    if op == "addc":
+    if op in ("addc", "addc_nc"):
         return f"v_addc_co_u32_e64 {x[1]}, {x[2]}, {fmt(x[3])}, {fmt(x[4])}, {x[5]}"
     if op == "add_co":
         return f"v_add_co_u32_e64 {x[1]}, {x[2]}, {fmt(x[3])}, {fmt(x[4])}"
@@ -940,7 +1081,7 @@ def outputs_after_inputs(g: Prog) -> bool:
     statement (no early-clobber "&"): the register allocator gets up to 8
     VGPRs per multiply back at the verify kernels' 128-VGPR budget."""
     seq = _all_reads(g)
-    is_in = re.compile(r"%\[(z\d+)?[ab]\d+\]")
+    is_in = re.compile(r"%\[(z\d+)?[abxy]\d+\]")
     is_out = re.compile(r"%\[(z\d+)?r\d+\]")
     last_in = max((i for i, x in enumerate(seq) if any(is_in.fullmatch(r) for r in reads(x))), default=-1)
     first_out = min((i for i, x in enumerate(seq) if any(is_out.fullmatch(w) for w in writes(x))), default=len(seq))
@@ -979,6 +1120,7 @@ def header() -> str:
     add = build("fe_add")
     sub = build("fe_sub")
     mont = build("sc_mont")
+    m2a = build("fe_mul2add")
     clob_m = ", ".join(f'"v{MONT_BASE + i}"' for i in range(MONT_NREGS))
     n_in = ", ".join(f'[n{i}] "v"({hex(N_LIMBS[i])}u)' for i in range(4))
     nc_in = ", ".join(f'[nc{i}] "v"({hex(N_C_LIMBS[i])}u)' for i in range(4))
@@ -988,6 +1130,9 @@ def header() -> str:
     b_in = ", ".join(f'[b{i}] "v"(b.v[{i}])' for i in range(8))
     r_out = ", ".join(f'[r{i}] "=&v"(r.v[{i}])' for i in range(8))
     assert outputs_after_inputs(mul) and outputs_after_inputs(sqr) and outputs_after_inputs(mont)
+    assert outputs_after_inputs(m2a)
+    x_in = ", ".join(f'[x{i}] "v"(x.v[{i}])' for i in range(8))
+    y_in = ", ".join(f'[y{i}] "v"(y.v[{i}])' for i in range(8))
     r_late = ", ".join(f'[r{i}] "=v"(r.v[{i}])' for i in range(8))  # outputs_after_inputs
     t_out = ", ".join(f'[t{i}] "=&v"(t[{i}])' for i in range(8))
     c_out = ", ".join(f'[c{i}] "=&s"(c{i})' for i in range(NCARRY))
@@ -1003,6 +1148,7 @@ def header() -> str:
 //   fe_add: {st['fe_add']}
 //   fe_sub: {st['fe_sub']}
 //   sc_mont: {st['sc_mont']}
+//   fe_mul2add: {st['fe_mul2add']}
 // The program lists are verified against Python integers by
 // tests/test_field_asm.py (interpreter in the generator), and end to end on
 // the GPU by the bit-exact parity tests.
@@ -1026,6 +1172,17 @@ __device__ __forceinline__ void fe_sqr_asm(fe &r, const fe &a) {{
 {asm_body(sqr)}
       : {r_late}, {c_out}
       : {a_in}
+      : {clob}, "scc");
+}}
+
+// r = a * b + x * y mod p (weak): one Comba pass over both products, one
+// fold.  Temporaries as fe_mul.
+__device__ __forceinline__ void fe_mul2add_asm(fe &r, const fe &a, const fe &b, const fe &x, const fe &y) {{
+  uint64_t {", ".join(f"c{i}" for i in range(NCARRY))};
+  asm volatile(
+{asm_body(m2a)}
+      : {r_late}, {c_out}
+      : {a_in}, {b_in}, {x_in}, {y_in}
       : {clob}, "scc");
 }}
 
