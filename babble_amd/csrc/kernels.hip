@@ -562,12 +562,7 @@ __global__ void __launch_bounds__(256) k_table_pair_g(const uint32_t *__restrict
   }
 }
 
-__global__ void __launch_bounds__(256) k_sinv(uint64_t n_items, uint32_t M, const uint32_t *__restrict__ s_be,
-                                              const uint8_t *__restrict__ pre, uint32_t *__restrict__ w_out) {
-  const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  sinv_thread(t, T, n_items, M, s_be, pre, w_out);
-}
+#include "sinv_kernels.h"  // k_sinv, k_sinv_block
 
 // Items [lo, hi) of a launch, lo a multiple of 64: each wave owns whole
 // 64-bit words of the accept bitmask (hi is a multiple of 64 or the end).
@@ -1599,7 +1594,14 @@ hipError_t build_tables(hipStream_t st, int kw, uint32_t n_bases, const uint32_t
 hipError_t sinv(hipStream_t st, uint64_t n, uint32_t M, const uint32_t *s_be, const uint8_t *pre, uint32_t *w) {
   if (n == 0) return hipSuccess;
   const uint64_t threads = (n + M - 1) / M;
-  hipLaunchKernelGGL(k_sinv, grid1(threads, 256), dim3(256), 0, st, n, M, s_be, pre, w);
+  // the latency shapes keep one inversion per lane: there k_sinv is on the
+  // step's critical path, and the barriers and the serial block stage behind
+  // the lanes cost more than the instructions they save (125k events: +2.6 %)
+  if (BV_SINV_BLOCK && !lat_variant(n))
+    hipLaunchKernelGGL(k_sinv_block<BV_SINV_THREADS>, grid1(threads, BV_SINV_THREADS), dim3(BV_SINV_THREADS), 0, st, n,
+                       M, s_be, pre, w);
+  else
+    hipLaunchKernelGGL(k_sinv, grid1(threads, 256), dim3(256), 0, st, n, M, s_be, pre, w);
   return hipGetLastError();
 }
 

@@ -279,9 +279,55 @@ DEV void gexz_set_ge(gexz &r, const fe &x, const fe &y) {
 // flagged item).  Without it a step with P == 0 leaves ZZ3 = ZZ1 P^2 == 0
 // (and finite garbage elsewhere), which the caller tests once after its last
 // addition.
-template <bool EXC = true>
-DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false) {
-  if (inf) {
+//
+// BV_Y_ALT (compile-time; 0 keeps the stored Y true; throughput forms with
+// BV_FUSED_Y3 only): the fused Y3 without its negation.  With YALT the step
+// computes the OPPOSITE of the sum: Y' = R (X3 - Q) + Y1 PPP = -Y3 — the
+// swapped subtraction is free and Y1 enters fe_mul2add as stored.  A chain of
+// such steps stores S and -S in turn (a state that is a function of the step
+// index alone, kept by the caller: verify_core.h), and in the -S state the
+// caller hands in the opposite entry (x2, -y2), whose sign it folds into the
+// lookup's conditional negation for nothing: -S + (-T) = -(S + T), and its
+// opposite is the true sum again.  P and X3 do not see the sign, R only
+// changes its own, so the exceptional cases are found as before.  Contract
+// with YALT: every path leaves the state flipped.  The rare paths pay for it
+// themselves: the doubling negates its Y, and for a lane at the identity the
+// caller passes the entry of the NEXT state (y2 negated once more), which is
+// copied.  A lane that adds nothing (digit 0: `take` false) negates its Y.
+#ifndef BV_Y_ALT
+#if defined(BV_DEFER_EXC) && BV_DEFER_EXC  // a build that asks for the deferred test: it has no alternating form
+#define BV_Y_ALT 0
+#else
+#define BV_Y_ALT 1
+#endif
+#endif
+#if !defined(__HIP_DEVICE_COMPILE__)
+// host builds (tests): entries into the rare paths of the XYZZ steps — a lane
+// that adds nothing, the identity taking an entry, P + P, P + (-P)
+struct bv_step_counts {
+  uint64_t skip, set, dbl, opp;
+};
+inline bv_step_counts &bv_step_count() {
+  static bv_step_counts c = {0, 0, 0, 0};
+  return c;
+}
+#define BV_STEP_COUNT(f) (bv_step_count().f++)
+#else
+#define BV_STEP_COUNT(f) ((void)0)
+#endif
+template <bool EXC = true, bool YALT = false>
+DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false,
+                     bool take = true) {
+  static_assert(!YALT || BV_FUSED_Y3, "the alternating Y is a form of the fused Y3");
+  // YALT: a lane that adds nothing (`take` false) shares the identity lanes'
+  // way out — one rare branch and one merge, as without the knob
+  if (inf || (YALT && !take)) {
+    if (YALT && !take) {
+      BV_STEP_COUNT(skip);
+      fe_neg(r.Y, r.Y);
+      return;
+    }
+    BV_STEP_COUNT(set);
     gexz_set_ge(r, x2, y2);
     inf = false;
     return;
@@ -294,9 +340,12 @@ DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_onl
   if ((EXC || chk) && fe_is_zero(P)) {
     if (fe_is_zero(R)) {
       gexz d;
+      BV_STEP_COUNT(dbl);
       gexz_double(d, r);
       r = d;
+      if (YALT) fe_neg(r.Y, r.Y);
     } else {
+      BV_STEP_COUNT(opp);
       inf = true;
     }
     return;
@@ -311,6 +360,12 @@ DEV void gexz_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_onl
   fe_sub(t, t, Q);
   fe_sub(r.X, t, Q);
   if (xz_only) return;
+  if (YALT) {  // -Y3 = R (X3 - Q) + Y1 PPP, ZZZ3 = ZZZ1 PPP
+    fe_sub(t, r.X, Q);
+    fe_mul(r.ZZZ, r.ZZZ, PPP);
+    fe_mul2add(r.Y, R, t, r.Y, PPP);
+    return;
+  }
   // Y3 = R (Q - X3) - Y1 PPP, ZZZ3 = ZZZ1 PPP
   fe_sub(t, Q, r.X);
 #if BV_FUSED_Y3
@@ -504,27 +559,34 @@ DEV void gexz_from_gej(gexz &r, const gej &a) {
   fe_mul(r.ZZZ, r.ZZ, a.Z);
 }
 
-template <bool LAT, bool EXC = true>
-DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false) {
+template <bool LAT, bool EXC = true, bool YALT = false>
+DEV void pt_add_ge(gexz &r, bool &inf, const fe &x2, const fe &y2, bool xz_only = false, bool chk = false,
+                   bool take = true) {
+  static_assert(!(LAT && YALT), "the latency variants keep the stored Y true");
   if (LAT) gexz_add_ge_lat(r, inf, x2, y2);  // latency variants always form the whole sum
-  else gexz_add_ge<EXC>(r, inf, x2, y2, xz_only, chk);
+  else gexz_add_ge<EXC, YALT>(r, inf, x2, y2, xz_only, chk, take);
 }
 
 // r += (x2, y2) for r AFFINE (ZZ = ZZZ = 1, not the identity: the first
 // table entry of a sum), mmadd-2008-s: 4M + 2S — the products by ZZ1 and
 // ZZZ1 of the general step drop out (U2 = x2, S2 = y2, ZZ3 = PP, ZZZ3 =
-// PPP).  Same exceptional cases as gexz_add_ge (and the same EXC / chk).
-template <bool LAT, bool EXC = true>
+// PPP).  Same exceptional cases as gexz_add_ge (and the same EXC / chk, and
+// the same YALT: the opposite of the sum, r never the identity here).
+template <bool LAT, bool EXC = true, bool YALT = false>
 DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2, bool chk = false) {
+  static_assert(!YALT || (BV_FUSED_Y3 && !LAT), "the alternating Y is a form of the fused Y3");
   fe P, R, PP, RR, PPP, Q, t, u, v;
   fe_sub(P, x2, r.X);
   fe_sub(R, y2, r.Y);
   if ((EXC || chk) && fe_is_zero(P)) {
     if (fe_is_zero(R)) {
       gexz d;
+      BV_STEP_COUNT(dbl);
       gexz_double(d, r);
       r = d;
+      if (YALT) fe_neg(r.Y, r.Y);
     } else {
+      BV_STEP_COUNT(opp);
       inf = true;
     }
     return;
@@ -544,7 +606,8 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2, bool ch
   fe_sub(t, RR, PPP);
   fe_sub(t, t, Q);
   fe_sub(t, t, Q);  // X3
-  fe_sub(u, Q, t);
+  if (YALT) fe_sub(u, t, Q);  // -Y3 = R (X3 - Q) + Y1 PPP
+  else fe_sub(u, Q, t);
   r.X = t;
   r.ZZ = PP;
   r.ZZZ = PPP;
@@ -554,6 +617,10 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2, bool ch
   } else
 #endif
   {
+    if (YALT) {
+      fe_mul2add(r.Y, R, u, r.Y, PPP);
+      return;
+    }
     if (BV_FUSED_Y3 && !LAT) {  // the throughput form: see gexz_add_ge
       fe_neg(v, r.Y);
       fe_mul2add(r.Y, R, u, v, PPP);
@@ -574,12 +641,20 @@ DEV void gexz_add_ge_aff(gexz &r, bool &inf, const fe &x2, const fe &y2, bool ch
 // variants at 2-3 waves per SIMD run 10-15 % slower; this per-lane form
 // stays.
 // `xz_only`: see gexz_add_ge (XYZZ throughput form only; ignored elsewhere).
-template <bool LAT, bool EXC = true>
+// YALT (BV_Y_ALT, see gexz_add_ge): a lane that adds nothing keeps step with
+// the others by negating its stored Y, inside gexz_add_ge.
+template <bool LAT, bool EXC = true, bool YALT = false>
 DEV void pt_add_ge_step(gexz &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false,
                         bool chk = false) {
-  if (take) pt_add_ge<LAT, EXC>(r, inf, x2, y2, xz_only, chk);
+  if (YALT) {
+    pt_add_ge<LAT, EXC, YALT>(r, inf, x2, y2, xz_only, chk, take);
+  } else if (take) {
+    pt_add_ge<LAT, EXC>(r, inf, x2, y2, xz_only, chk);
+  } else {
+    BV_STEP_COUNT(skip);
+  }
 }
-template <bool LAT, bool EXC = true>
+template <bool LAT, bool EXC = true, bool YALT = false>
 DEV void pt_add_ge_step(gej &r, bool &inf, const fe &x2, const fe &y2, bool take, bool xz_only = false,
                         bool chk = false) {
   if (take) gej_add_ge_sel<LAT>(r, inf, x2, y2);

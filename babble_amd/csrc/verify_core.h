@@ -468,13 +468,15 @@ DEV bool s_usable(const uint8_t *pre, uint64_t i, const sc &s) {
 // inverse of the total (xR -> x^-1 R) is R^(1+K) / prod s, one extra
 // product by 1 makes it R^K / prod s, and walking back w_k = inv acc_(k-1)
 // / R = R / s_k while inv loses one s_k and one R per step.
-DEV void sinv_thread(uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const uint32_t *s_be, const uint8_t *pre,
-                     uint32_t *w_out) {
-  sc R1, one;
-  sc_load_const(R1, SC_R1);
+// The two halves of a lane's walk, split so that k_sinv_block can put the
+// block stage between them: the prefix products go to w_out and the lane's
+// total acc_K comes back; the walk back takes inv = R / acc_K = R^K / prod s.
+DEV void sinv_lane_prefix(sc &acc, uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const uint32_t *s_be,
+                          const uint8_t *pre, uint32_t *w_out) {
+  sc one;
 #pragma unroll
   for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u;
-  sc acc = R1;
+  sc_load_const(acc, SC_R1);
   for (uint32_t m = 0; m < M; m++) {
     const uint64_t i = t + (uint64_t)m * T;
     if (i >= n_items) break;
@@ -486,9 +488,13 @@ DEV void sinv_thread(uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const
     q[1] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
     sc_mont(acc, acc, s);
   }
-  sc inv;
-  sc_inverse_var(inv, acc);
-  sc_mont(inv, inv, one);
+}
+
+DEV void sinv_lane_finish(sc inv, uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const uint32_t *s_be,
+                          const uint8_t *pre, uint32_t *w_out) {
+  sc one;
+#pragma unroll
+  for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u;
   for (int m = (int)M - 1; m >= 0; m--) {
     const uint64_t i = t + (uint64_t)m * T;
     if (i >= n_items) continue;
@@ -503,6 +509,70 @@ DEV void sinv_thread(uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const
     sc_mont(inv, inv, s);
     q[0] = make_uint4(w.v[0], w.v[1], w.v[2], w.v[3]);
     q[1] = make_uint4(w.v[4], w.v[5], w.v[6], w.v[7]);
+  }
+}
+
+DEV void sinv_thread(uint64_t t, uint64_t T, uint64_t n_items, uint32_t M, const uint32_t *s_be, const uint8_t *pre,
+                     uint32_t *w_out) {
+  sc acc, inv, one;
+#pragma unroll
+  for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u;
+  sinv_lane_prefix(acc, t, T, n_items, M, s_be, pre, w_out);
+  sc_inverse_var(inv, acc);
+  sc_mont(inv, inv, one);
+  sinv_lane_finish(inv, t, T, n_items, M, s_be, pre, w_out);
+}
+
+// BV_SINV_BLOCK (compile-time; 0 restores one inversion per lane): a second
+// level of Montgomery's trick inside the block.  Every lane's total A_t =
+// acc_K is a canonical non-zero residue (a lane with no items holds R, a
+// Montgomery one), and all the lane needs back is R / A_t.  That is the
+// invariant above once more with the A_t in the place of the s_k: lane j of
+// the L lanes of one wave takes the totals j, j + L, ... below B, forms
+// their prefix products R^(1-k) prod A, inverts once, and walks back
+// out_k = R / A_k.  So a block of B lanes runs L inversion sequences on one
+// wave instead of B on B / 64 waves, for 3 B / L extra products on that wave.
+// `tot` and `out` hold B scalars of 8 words (LDS on the device, between two
+// barriers); sc_mont results are canonical, so w is bit for bit the per-lane
+// form's.
+#ifndef BV_SINV_BLOCK
+#define BV_SINV_BLOCK 1
+#endif
+#ifndef BV_SINV_THREADS  // lanes per k_sinv_block block (a multiple of 64)
+#define BV_SINV_THREADS 256
+#endif
+
+DEV void sinv_block_lane(uint32_t j, uint32_t L, uint32_t B, const uint32_t *tot, uint32_t *out) {
+  if (j >= B) return;
+  sc acc, inv, one;
+#pragma unroll
+  for (int k = 0; k < 8; k++) one.v[k] = k == 0 ? 1u : 0u;
+  sc_load_const(acc, SC_R1);
+  uint32_t last = j;
+  for (uint32_t k = j; k < B; k += L) {
+    sc a;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      a.v[i] = tot[8 * k + i];
+      out[8 * k + i] = acc.v[i];
+    }
+    sc_mont(acc, acc, a);
+    last = k;
+  }
+  sc_inverse_var(inv, acc);
+  sc_mont(inv, inv, one);
+  for (uint32_t k = last;; k -= L) {
+    sc a, pfx, w;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      a.v[i] = tot[8 * k + i];
+      pfx.v[i] = out[8 * k + i];
+    }
+    sc_mont(w, inv, pfx);  // R / A_k
+    sc_mont(inv, inv, a);
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[8 * k + i] = w.v[i];
+    if (k < L) break;
   }
 }
 
@@ -644,6 +714,22 @@ DEV bool final_check(const gexz &R, bool inf, const fe &r) {
 #ifndef BV_DEFER_EXC
 #define BV_DEFER_EXC 0
 #endif
+// BV_Y_ALT (point.h: the additions store S and -S in turn and form no
+// negation for the fused Y3) in the pipelined throughput loops.  The state —
+// whether the accumulator holds the opposite of the sum — is a function of
+// the step index alone: a loop entered in state y0 runs window j in state
+// y0 ^ (j & 1) and leaves y0 ^ (NWIN & 1), all wave-uniform; the callers
+// below carry it from loop to loop in one bool and put a true Y back
+// (y_true) wherever an accumulator is stored or handed to code that does not
+// alternate.  The deferred exception test (above) has no alternating form.
+static_assert(!(BV_Y_ALT && BV_DEFER_EXC), "BV_Y_ALT and BV_DEFER_EXC are alternatives");
+constexpr bool y_alt(bool lat, int pipe_bit) {
+  return BV_Y_ALT != 0 && BV_FUSED_Y3 != 0 && (BV_LOOKUP_PIPE & pipe_bit) != 0 && !lat;
+}
+DEV void y_true(gexz &R, bool &yn) {
+  if (yn) fe_neg(R.Y, R.Y);
+  yn = false;
+}
 #if !defined(__HIP_DEVICE_COMPILE__)
 // host builds (tests): items that took the second, checked pass
 inline uint64_t &bv_defer_redo_count() {
@@ -786,11 +872,15 @@ DEV uint32_t next_digit(uint32_t *u, uint32_t &carry, bool &dneg) {
 // top window's addition is the trimmed one (gexz_add_ge xz_only).
 // DEFER (pipelined XYZZ loop only): the additions test P only when `chk`
 // (BV_DEFER_EXC above); the caller tests ZZ after its last loop.
+// YALT (pipelined XYZZ loop only; BV_Y_ALT above): *ys is the accumulator's
+// state, read on entry and updated on return.
 template <int W, int NWIN, bool LAT = false, class PT = gej, bool FROM_INF = false, bool FINAL = false,
-          bool DEFER = false>
-DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool chk = false) {
+          bool DEFER = false, bool YALT = false>
+DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool chk = false, bool *ys = nullptr) {
   constexpr uint32_t ENT = 1u << (W - 1);
   static_assert(W * NWIN >= 257 && W < 32, "signed G windows must absorb the last carry");
+  static_assert(!YALT || (y_alt(LAT, 1) && std::is_same<PT, gexz>::value),
+                "alternating Y only in the pipelined throughput loop");
   static_assert(!DEFER || ((BV_LOOKUP_PIPE & 1) && !LAT && std::is_same<PT, gexz>::value),
                 "deferred additions only in the pipelined throughput loop");
   uint32_t carry = 0;
@@ -799,12 +889,19 @@ DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool 
     bool dneg;
     uint32_t d = next_digit<W, 8, true>(u, carry, dneg);
     stage.request(tab + (uint64_t)d * BV_ENTRY_U32);  // d == 0: the window's slot 0, valid and not added
+    bool y0 = false;
+    if constexpr (YALT) {
+      y0 = *ys;
+      *ys = y0 != ((NWIN & 1) != 0);
+    }
 #pragma unroll 1
     for (int j = 0; j < NWIN; j++) {
       fe x, y;
       stage.take(x, y);
       const uint32_t dj = d;
-      const bool nj = dneg;
+      // YALT: the opposite entry in the -S state, and for a lane at the
+      // identity the entry of the state it enters (gexz_add_ge)
+      const bool nj = YALT ? (dneg != (y0 != ((j & 1) != 0))) != inf : dneg;
       if (j + 1 < NWIN) {  // the same recoding as the entry consumed next: never an address off the table
         d = next_digit<W, 8, true>(u, carry, dneg);
         stage.request(tab + ((uint64_t)(j + 1) * ENT + d) * BV_ENTRY_U32);
@@ -812,11 +909,16 @@ DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool 
       fe_cneg_canon(y, nj);
       if constexpr (FROM_INF) {
         if (j == 1 && !inf) {  // R = window 0's entry (affine)
-          if (dj != 0) gexz_add_ge_aff<LAT, !DEFER>(R, inf, x, y, chk);
+          if (dj != 0) {
+            gexz_add_ge_aff<LAT, !DEFER, YALT>(R, inf, x, y, chk);
+          } else {
+            BV_STEP_COUNT(skip);
+            if (YALT) fe_neg(R.Y, R.Y);
+          }
           continue;
         }
       }
-      pt_add_ge_step<LAT, !DEFER>(R, inf, x, y, dj != 0, FINAL && j == NWIN - 1, chk);
+      pt_add_ge_step<LAT, !DEFER, YALT>(R, inf, x, y, dj != 0, FINAL && j == NWIN - 1, chk);
     }
     return;
   }
@@ -939,7 +1041,9 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
     fe_set(R.Y, 0);
     fe_set(R.ZZ, 0);
     fe_set(R.ZZZ, 0);
-    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER>(R, inf, g_table, u, chk);
+    bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum
+    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER, y_alt(LAT, 1)>(R, inf, g_table, u, chk, &yn);
+    y_true(R, yn);  // R_G is stored with its true Y
     if constexpr (DEFER) {
       // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC).  On this
       // chain it cannot happen (the partial sums
@@ -972,11 +1076,13 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
 // entries and negating back gives, without the two field negations.
 // `last` (uniform; XYZZ throughput form): only X and ZZ of the sum are read
 // afterwards, so the top window's addition is the trimmed one.
-// DEFER / chk: as g_table_add.
-template <int W, int NWIN, bool SIGNED, bool LAT = false, class PT = gexz, bool DEFER = false>
+// DEFER / chk, YALT / ys: as g_table_add.
+template <int W, int NWIN, bool SIGNED, bool LAT = false, class PT = gexz, bool DEFER = false, bool YALT = false>
 DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], bool neg, bool phi = false,
-                       bool from_inf = false, bool last = false, bool chk = false) {
+                       bool from_inf = false, bool last = false, bool chk = false, bool *ys = nullptr) {
   constexpr uint32_t ENT = SIGNED ? (1u << (W - 1)) : (1u << W);
+  static_assert(!YALT || (y_alt(LAT, 2) && std::is_same<PT, gexz>::value),
+                "alternating Y only in the pipelined throughput loop");
   static_assert(!SIGNED || W * NWIN >= 129, "signed windows must absorb the last carry");
   static_assert(!DEFER || ((BV_LOOKUP_PIPE & 2) && !LAT && std::is_same<PT, gexz>::value),
                 "deferred additions only in the pipelined throughput loop");
@@ -986,12 +1092,18 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
     bool dneg;
     uint32_t d = next_digit<W, 4, SIGNED>(k, carry, dneg);
     stage.request(tab + (uint64_t)d * BV_ENTRY_U32);  // d == 0: a valid, unused slot
+    bool y0 = false;
+    if constexpr (YALT) {
+      y0 = *ys;
+      *ys = y0 != ((NWIN & 1) != 0);
+    }
 #pragma unroll 1
     for (int j = 0; j < NWIN; j++) {
       fe x, y;
       stage.take(x, y);
       const uint32_t dj = d;
-      const bool nj = dneg != neg;
+      // YALT: as g_table_add, folded into the same sign as the half's
+      const bool nj = YALT ? ((dneg != neg) != (y0 != ((j & 1) != 0))) != inf : dneg != neg;
       if (j + 1 < NWIN) {  // the same recoding as the entry consumed next: never an address off the table
         d = next_digit<W, 4, SIGNED>(k, carry, dneg);
         stage.request(tab + ((uint64_t)(j + 1) * ENT + d) * BV_ENTRY_U32);
@@ -1003,10 +1115,15 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
       }
       fe_cneg_canon(y, nj);
       if (from_inf && j == 1 && !inf) {  // R = window 0's entry (affine)
-        if (dj != 0) gexz_add_ge_aff<LAT, !DEFER>(R, inf, x, y, chk);
+        if (dj != 0) {
+          gexz_add_ge_aff<LAT, !DEFER, YALT>(R, inf, x, y, chk);
+        } else {
+          BV_STEP_COUNT(skip);
+          if (YALT) fe_neg(R.Y, R.Y);
+        }
         continue;
       }
-      pt_add_ge_step<LAT, !DEFER>(R, inf, x, y, dj != 0, last && j == NWIN - 1, chk);
+      pt_add_ge_step<LAT, !DEFER, YALT>(R, inf, x, y, dj != 0, last && j == NWIN - 1, chk);
     }
     return;
   }
@@ -1081,12 +1198,14 @@ DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, cons
     constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
     lane_park park;
     if (PARK) park.put(k2);
+    bool yn = false;  // BV_Y_ALT: R_G comes with its true Y; final_check reads no Y
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
       uint32_t kk[4];
       glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u,
-                                                       KC && h, false, h == 1, chk);
+      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab + (h && !KC ? half : 0), kk,
+                                                                      (signs >> h) & 1u, KC && h, false, h == 1, chk,
+                                                                      &yn);
     }
     if constexpr (DEFER) {
       // ZZ == 0 <=> some step of either half had P == 0 (the lemma at
@@ -1153,13 +1272,16 @@ DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, co
     constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
     lane_park park;
     if (PARK) park.put(k2);
+    bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
       uint32_t kk[4];
       glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER>(R, inf, tab + (h && !KC ? half : 0), kk, (signs >> h) & 1u,
-                                                       KC && h, h == 0, false, chk);
+      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab + (h && !KC ? half : 0), kk,
+                                                                      (signs >> h) & 1u, KC && h, h == 0, false, chk,
+                                                                      &yn);
     }
+    y_true(R, yn);  // R_Q is stored with its true Y
     if constexpr (DEFER) {
       // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC; the
       // chain starts from the identity).  The flagged item starts again from
@@ -1204,6 +1326,8 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
     gexz R;
     bool inf;
     rg_load(rq, n, i, R, inf);
+    // BV_Y_ALT is not applied here: the alternating form raised k_verify_gf's
+    // scratch (44 -> 48 B), and this kernel waits for PCIe, not for its VALU
     g_table_add<BV_GW, BV_GNWIN, LAT, gexz, false, true, DEFER>(R, inf, g_table, u, chk);
     if constexpr (DEFER) {
       // ZZ == 0 <=> some G step had P == 0 (the lemma at BV_DEFER_EXC; R_Q
@@ -1250,7 +1374,9 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
     fe_set(R.Y, 0);
     fe_set(R.ZZ, 0);
     fe_set(R.ZZZ, 0);
-    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER>(R, inf, g_table, u, chk);
+    bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum; final_check reads no Y
+    g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER, y_alt(LAT, 1)>(R, inf, g_table, u, chk, &yn);
+    if (!y_alt(LAT, 2)) y_true(R, yn);
     constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
     lane_park park;
     if (PARK) park.put(k2);
@@ -1258,7 +1384,8 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
     for (int h = 0; h < 2; h++) {
       uint32_t kk[4];
       glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, true, LAT, gexz, DEFER>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false, h == 1, chk);
+      key_table_add<W, NWIN, true, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false,
+                                                                    h == 1, chk, &yn);
     }
     if constexpr (DEFER) {
       // ZZ == 0 <=> some step of the G chain or of either half had P == 0
