@@ -1474,7 +1474,7 @@ static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
     HIPCHK(hipMemsetAsync(ctx->d_stamps.p, 0, 16 * 8, st), BV_E_LAUNCH, "memset stamps");
     stamps = ctx->d_stamps.as<uint64_t>();
   }
-  HIPCHK(bvk::verify_small(st, (uint32_t)n_items, dev + o_dig, dev + o_key, (const uint64_t *)(dev + o_koff),
+  HIPCHK(bvk::verify_small(st, ctx->kc_w, (uint32_t)n_items, dev + o_dig, dev + o_key, (const uint64_t *)(dev + o_koff),
                            (const uint32_t *)(dev + o_im), (const uint32_t *)(dev + o_ik), dev + o_r, dev + o_s,
                            b->pre ? dev + o_pre : nullptr, kc ? (const uint64_t *)(dev + o_tab) : nullptr,
                            ctx->g_table, dev + o_st, stamps, recs ? (const uint32_t *)(dev + o_rec) : nullptr,
@@ -1519,7 +1519,7 @@ static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
     const uint64_t start = clk[0];
     t.ms_total = t.ms_verify = start && end >= start ? (float)((double)(end - start) / ctx->wall_khz) : 0.f;
   }
-  t.key_path = kc && hits ? BV_KCW : 0;
+  t.key_path = kc && hits ? ctx->kc_w : 0;  // the geometry of the tables k_small read (22, or 18: bv_kc_small_tables)
   t.kc_hits = hits;
   t.kc_keys = (uint32_t)ctx->kc_index.size();
   t.ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -74,7 +74,8 @@ hipError_t verify_g(hipStream_t, uint64_t, uint64_t, uint64_t, const uint32_t *,
 hipError_t verify_q(hipStream_t, int, uint64_t, uint64_t, uint64_t, const uint32_t *, const uint32_t *,
                     const uint32_t *, const uint8_t *, const uint8_t *, const uint32_t *, const uint32_t *,
                     const uint64_t *, const uint32_t *, uint8_t *, uint64_t *);
-hipError_t verify_small(hipStream_t, uint32_t n_items, const uint8_t *dig, const uint8_t *key_bytes,
+// kw: the geometry of kc_tabs' and the records' tables, 22 or 18
+hipError_t verify_small(hipStream_t, int kw, uint32_t n_items, const uint8_t *dig, const uint8_t *key_bytes,
                         const uint64_t *key_off, const uint32_t *item_msg, const uint32_t *item_key,
                         const uint8_t *r_be, const uint8_t *s_be, const uint8_t *pre, const uint64_t *kc_tabs,
                         const uint32_t *g_table, uint8_t *status, uint64_t *stamps, const uint32_t *rec,
@@ -304,6 +305,10 @@ struct bv_ctx {
   // The ONE cached geometry of this context, fixed at bv_create: 22 (KC, 805
   // MB per key) or, with BV_F_KC_COMPACT, 18 (KC18, 67.1 MB per key).
   int kc_w = BV_KCW;
+  // bv_kc_small_tables: a compact context's small batches read its KC18
+  // tables (k_small<18, 8>).  Off: they run as for keys without a table.
+  // A 22-bit context's always read theirs (bv_keycache.cpp kc_small_readable).
+  bool kc_small_tables = false;
   uint64_t kc_table_bytes = 0, kc_sub_bytes = 0, kc_pscr_bytes = 0;  // per key, of kc_w (bv_kc_init)
   uint32_t kc_build_group = 0;  // keys per table-build launch (bounds the build scratch)
   std::unordered_map<std::string, int> kc_index;  // keys whose table build has been enqueued

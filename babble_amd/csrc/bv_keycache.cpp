@@ -377,12 +377,16 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
 // Host-only lookup for the small-batch path (no device work, no sync): the
 // table of every batch key that has one built, else 0.  Small batches never
 // build tables (registration and bulk batches do).  Returns the hits.
-// k_small's warm tree has one leaf per KC window (kSmallLeaves), so a KC18
-// context gives it no tables and 0 hits: its small batches run as for keys
-// without a table, and the tables serve the bulk pipeline.
+// The tables are of the context's geometry, and bv_api.cpp launches the
+// k_small instantiation of that geometry.  A compact (KC18) context hands
+// its tables over only after bv_kc_small_tables(ctx, 1); until then it
+// gives no tables and 0 hits: its small batches run as for keys without a
+// table, and the tables serve the bulk pipeline.
+static bool kc_small_readable(const bv_ctx *ctx) { return ctx->kc_w == BV_KCW || ctx->kc_small_tables; }
+
 uint32_t bv_kc_lookup(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko, uint64_t *tabs) {
   uint32_t hits = 0;  // distinct keys, as bv_kc_prepare counts them
-  if (ctx->kc_w != BV_KCW) {
+  if (!kc_small_readable(ctx)) {
     for (uint32_t k = 0; k < n_keys; k++) tabs[k] = 0;
     return 0;
   }
@@ -401,9 +405,9 @@ uint32_t bv_kc_lookup(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const ui
 }
 
 // Every well-formed key of the batch has a built table that k_small can
-// read (host-only): never on a KC18 context (bv_kc_lookup).
+// read (host-only): on a KC18 context only with bv_kc_small_tables on.
 bool bv_kc_all_cached(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko) {
-  if (ctx->kc_w != BV_KCW) return false;
+  if (!kc_small_readable(ctx)) return false;
   for (uint32_t k = 0; k < n_keys; k++) {
     if (!key_form_ok(hkb + hko[k], hko[k + 1] - hko[k])) continue;
     if (!ctx->kc_index.count(std::string((const char *)hkb + hko[k], (size_t)(hko[k + 1] - hko[k])))) return false;
@@ -446,5 +450,16 @@ extern "C" int bv_kc_register(bv_ctx *ctx, uint32_t n_keys, const uint8_t *key_b
   rc = bv_mark_done(ctx, st);
   if (rc != BV_OK) return bv_drain(ctx, st, rc);
   HIPCHK(bv_host_wait(ctx, st), BV_E_LAUNCH, "sync");
+  return BV_OK;
+}
+
+// Host state only: which tables bv_kc_lookup / bv_kc_all_cached hand to the
+// small-batch path from the next call on.
+extern "C" int bv_kc_small_tables(bv_ctx *ctx, int on) {
+  if (!ctx) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!(ctx->flags & BV_F_KC_COMPACT))
+    return bv_fail(ctx, BV_E_ARGS, "bv_kc_small_tables needs BV_F_KC_COMPACT (22-bit tables are always read)");
+  ctx->kc_small_tables = on != 0;
   return BV_OK;
 }

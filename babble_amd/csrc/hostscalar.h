@@ -29,7 +29,7 @@ constexpr uint32_t kS = 28;
 constexpr uint32_t kU1 = 36;      // u1 = e s^-1 mod N, 8 little-endian limbs
 constexpr uint32_t kK = 44;       // |k1| (4 limbs), |k2| (4 limbs): u2 = k1 + k2 lambda
 constexpr uint32_t kSigns = 52;   // bit 0: k1 < 0, bit 1: k2 < 0
-constexpr uint32_t kTab = 54;     // the key cache's table address (u64; 0: none)
+constexpr uint32_t kTab = 54;     // the key cache's table address (u64; 0: none), a table of the context's geometry
 }  // namespace hrec
 
 // One item's inputs: the SHA-256 digest of its message, r and s (32

@@ -806,10 +806,12 @@ __global__ void __launch_bounds__(64) k_verify_deferred(uint64_t n, const uint32
 //   phase 2  wave 0 lane 0: decision table, u1 = e w;  wave 1 lane 0:
 //            u2 = r w, its GLV split (k1, k2, signs) and, without a table,
 //            the chain length and the phase count; wave 2: kColdD1 doublings
-//   phase 3  key with a key-cache table: 22 leaves in lanes 0..21 of wave
-//            0, every table entry loaded at once — G windows 0..9 of u1,
-//            KC windows 0..5 of k1 (T) and of k2 (phi(T)) — summed by a
-//            binary tree (affine pairs, then XYZZ sums: 5 levels of zipped
+//   phase 3  key with a key-cache table of the geometry <KW, KNWIN> the
+//            kernel is instantiated for (KC <22, 6>, KC18 <18, 8>): 22 / 26
+//            leaves in lanes 0..21 / 0..25 of wave 0, every table entry
+//            loaded at once — G windows 0..9 of u1, table windows
+//            0..KNWIN-1 of k1 (T) and of k2 (phi(T)), small_table_leaf —
+//            summed by a tree (affine pairs, then XYZZ sums: 5 levels of
 //            point additions, nodes handed over through LDS);
 //            key without one: right to left in barrier-separated phases
 //            (see SmallCold above): wave 2 doubles kColdChunk more entries
@@ -822,7 +824,6 @@ __global__ void __launch_bounds__(64) k_verify_deferred(uint64_t n, const uint32
 // (BV_SMALL_STAMPS diagnostics): workgroup 0's shader clocks per phase.
 // ---------------------------------------------------------------------------
 namespace {
-constexpr int kSmallLeaves = BV_GNWIN + 2 * BV_KCNWIN;  // 22
 struct SmallNode {
   uint32_t w[33];
 };
@@ -1031,10 +1032,20 @@ __device__ __forceinline__ void coop_sum_nodes(const SmallNode *from, uint32_t l
   row_store(to.w, X), row_store(to.w + 8, Y), row_store(to.w + 16, ZZ), row_store(to.w + 24, ZZZ);
   if (__lane_id() == 0) to.w[32] = inf ? 1u : 0u;
 }
-// the warm tree's first level: wave w sums leaf-pair nodes [kWarmSplit[w], kWarmSplit[w + 1])
-constexpr uint32_t kWarmSplit[5] = {0, 3, 6, 9, (kSmallLeaves + 1) / 2};
+// the warm tree's first level, per cached geometry: wave w sums leaf-pair
+// nodes [kWarmSplit<KNWIN>[w], kWarmSplit<KNWIN>[w + 1]) — 3/3/3/2 of KC's 11
+// nodes, 4/3/3/3 of KC18's 13
+template <int KNWIN>
+constexpr uint32_t kWarmSplit[5] = {};
+template <>
+constexpr uint32_t kWarmSplit<BV_KCNWIN>[5] = {0, 3, 6, 9, small_warm<BV_KCNWIN>::kNodes};
+template <>
+constexpr uint32_t kWarmSplit<BV_KC18NWIN>[5] = {0, 4, 7, 10, small_warm<BV_KC18NWIN>::kNodes};
 }  // namespace
 
+// <KW, KNWIN>: the cached geometry of the tables in kc_tabs / the records
+// (KC <22, 6> or KC18 <18, 8>); nothing else depends on it.
+template <int KW, int KNWIN>
 __global__ void __launch_bounds__(256) k_small(uint32_t n_items, const uint32_t *__restrict__ digest_words,
                                                const uint8_t *__restrict__ key_bytes,
                                                const uint64_t *__restrict__ key_off,
@@ -1067,6 +1078,9 @@ __global__ void __launch_bounds__(256) k_small(uint32_t n_items, const uint32_t 
   __shared__ uint64_t sh_tab;
   __shared__ SinvMail sh_mail;
   __shared__ uint32_t sh_sok, sh_cls;
+  constexpr int kSmallLeaves = small_warm<KNWIN>::kLeaves;  // 22 / 26: the node arrays are sized per geometry
+  static_assert(kWarmSplit<KNWIN>[0] == 0 && kWarmSplit<KNWIN>[4] == small_warm<KNWIN>::kNodes,
+                "a first-level split for this geometry");
   __shared__ SmallNode sh_a[kSmallLeaves], sh_b[kSmallLeaves / 2 + 1], sh_c[kSmallLeaves / 4 + 2];
   __shared__ SmallCold cs;
   __shared__ uint32_t sh_rec[hrec::kWords];
@@ -1260,15 +1274,10 @@ __global__ void __launch_bounds__(256) k_small(uint32_t n_items, const uint32_t 
         for (int k = 0; k < 8; k++) u[k] = sh_u1[k];
         table_leaf<BV_GW, 8>(x, y, zero, g_table, u, (int)lane, false, false);
       } else if (lane < (uint32_t)kSmallLeaves) {  // KC window j of k1 (T) or of k2 (phi(T))
-        const uint32_t q = lane - BV_GNWIN, h = q / BV_KCNWIN;
-        uint32_t kk[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) kk[k] = sh_k[4 * h + k];
-        table_leaf<BV_KCW, 4>(x, y, zero, (const uint32_t *)tab, kk, (int)(q % BV_KCNWIN), (signs >> h) & 1u,
-                              h != 0);
+        small_table_leaf<KW, KNWIN>(x, y, zero, (const uint32_t *)tab, sh_k, signs, lane - BV_GNWIN);
       }
       if (lane == 0) SMALL_STAMP(7);
-      small_leaf_pairs(x, y, zero, sh_b, sh_a, kSmallLeaves, lane);  // 22 leaves -> 11 nodes (per lane)
+      small_leaf_pairs(x, y, zero, sh_b, sh_a, kSmallLeaves, lane);  // 22 leaves -> 11 nodes, 26 -> 13 (per lane)
       if (lane == 0) SMALL_STAMP(8);
     } else if (rec && wave == 2 && lane == 0) {  // the record's key, decoded off the critical path
       uint8_t st;
@@ -1278,9 +1287,9 @@ __global__ void __launch_bounds__(256) k_small(uint32_t n_items, const uint32_t 
     }
     __syncthreads();
     // the XYZZ tree on DPP rows (coop.h add_xyzz, ~6k clocks an addition
-    // against ~21k for one lane's): 11 -> 4 (wave w sums nodes
+    // against ~21k for one lane's): 11 or 13 -> 4 (wave w sums nodes
     // kWarmSplit[w] .. kWarmSplit[w + 1] - 1), 4 -> 2 (waves 0, 1), 2 -> 1
-    coop_sum_nodes(sh_b, kWarmSplit[wave], kWarmSplit[wave + 1], sh_c[wave]);
+    coop_sum_nodes(sh_b, kWarmSplit<KNWIN>[wave], kWarmSplit<KNWIN>[wave + 1], sh_c[wave]);
     __syncthreads();
     if (wave < 2) {
       coop_sum_nodes(sh_c, 2 * wave, 2 * wave + 2, sh_a[wave]);
@@ -1770,15 +1779,25 @@ hipError_t build_kc(hipStream_t st, int kw, uint32_t n, const uint32_t *kxy, con
 
 // (no timing events around a latency-bound launch: the kernel writes its
 // own span on the constant clock into `clk`, host memory)
-hipError_t verify_small(hipStream_t st, uint32_t n_items, const uint8_t *dig, const uint8_t *key_bytes,
+// kw = 22 / 18: the geometry of the tables in kc_tabs and the records (with
+// neither, either instantiation computes the same; the context's is taken).
+hipError_t verify_small(hipStream_t st, int kw, uint32_t n_items, const uint8_t *dig, const uint8_t *key_bytes,
                         const uint64_t *key_off, const uint32_t *item_msg, const uint32_t *item_key,
                         const uint8_t *r_be, const uint8_t *s_be, const uint8_t *pre, const uint64_t *kc_tabs,
                         const uint32_t *g_table, uint8_t *status, uint64_t *stamps, const uint32_t *rec,
                         uint64_t *clk) {
+  if (kw != BV_KCW && kw != BV_KC18W) return hipErrorInvalidValue;
   if (n_items == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_small, dim3(n_items), dim3(256), 0, st, n_items, (const uint32_t *)dig, key_bytes, key_off,
-                     item_msg, item_key, (const uint32_t *)r_be, (const uint32_t *)s_be, pre, kc_tabs, g_table,
-                     status, stamps, rec, clk);
+#define BV_LAUNCH_SMALL(KW, KNWIN)                                                                                   \
+  hipLaunchKernelGGL((k_small<KW, KNWIN>), dim3(n_items), dim3(256), 0, st, n_items, (const uint32_t *)dig,          \
+                     key_bytes, key_off, item_msg, item_key, (const uint32_t *)r_be, (const uint32_t *)s_be, pre,    \
+                     kc_tabs, g_table, status, stamps, rec, clk);
+  if (kw == BV_KCW) {
+    BV_LAUNCH_SMALL(BV_KCW, BV_KCNWIN)
+  } else {
+    BV_LAUNCH_SMALL(BV_KC18W, BV_KC18NWIN)
+  }
+#undef BV_LAUNCH_SMALL
   return hipGetLastError();
 }
 

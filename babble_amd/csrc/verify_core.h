@@ -1538,8 +1538,10 @@ DEV void naf_mul(gej &R, bool &inf, const fe &px, const fe &py, const uint32_t k
 // XOR `neg` (the GLV half's sign); `phi`: (beta x, y) of the stored entry;
 // *zero: the digit is 0 (the leaf is the identity).  The recoding runs over
 // windows 0..j (a digit depends on the carry out of the window below).
+// Returns the slot it read, j ENT + |d| (the CPU replay of the warm leaves,
+// tests/kcsmall, holds it to the stored slots; the kernels drop it).
 template <int W, int NW>
-DEV void table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, uint32_t u[NW], int j, bool neg, bool phi) {
+DEV uint64_t table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, uint32_t u[NW], int j, bool neg, bool phi) {
   constexpr uint32_t ENT = 1u << (W - 1);
   uint32_t carry = 0, d = 0;
   for (int w = 0; w <= j; w++) {
@@ -1552,7 +1554,8 @@ DEV void table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, uint32_t u[NW
   const bool dneg = carry != 0;
   if (dneg) d = (1u << W) - d;  // |d - 2^W|, 0 when d == 2^W
   zero = d == 0;
-  const uint32_t *e = tab + ((uint64_t)j * ENT + d) * BV_ENTRY_U32;  // d == 0: a valid, unused slot
+  const uint64_t slot = (uint64_t)j * ENT + d;
+  const uint32_t *e = tab + slot * BV_ENTRY_U32;  // d == 0: a valid, unused slot
   fe_load4(x, e);
   fe_load4(y, e + 8);
   if (phi) {
@@ -1561,6 +1564,39 @@ DEV void table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, uint32_t u[NW
     fe_mul(x, x, beta);
   }
   fe_cneg_canon(y, dneg != neg);
+  return slot;
+}
+
+// Leaves of k_small's warm tree (a key with a key-cache table of the cached
+// geometry <KW, KNWIN>: KC <22, 6> or KC18 <18, 8>): BV_GNWIN G leaves, then
+// 2 KNWIN table leaves.
+template <int KNWIN>
+struct small_warm {
+  static constexpr int kLeaves = BV_GNWIN + 2 * KNWIN;  // 22 (KC), 26 (KC18)
+  static constexpr int kNodes = (kLeaves + 1) / 2;      // XYZZ nodes after the leaf pairs: 11, 13
+};
+// Table leaf q of 2 KNWIN (lane BV_GNWIN + q of wave 0): q < KNWIN is window q
+// of k1 on T, the others window q - KNWIN of k2 on phi(T) = (beta x, y) of
+// the same stored entries.  k12 = k1[4] | k2[4] (magnitudes), signs bit h =
+// half h is negative.  The layout is verify_item_q's for a cached W: ONE
+// stored half of KNWIN 2^(KW-1) + 1 entries (BV_KCHALF_U32 / BV_KC18HALF_U32),
+// slot j ENT + |d| with |d| <= ENT, so every read is inside the allocation:
+// a zero digit reads slot j ENT (the digit ENT of window j - 1 for j >= 1,
+// the never-written slot 0 for j = 0; the leaf is flagged zero either way),
+// and a half below 2^128 leaves the top window of KC18 (bits 126, 127 and
+// the carry) digits 0..4, all in the first stored block of its window.
+template <int KW, int KNWIN>
+DEV uint64_t small_table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, const uint32_t k12[8], uint32_t signs,
+                              uint32_t q) {
+  static_assert(BV_W_IS_CACHED(KW) && KW * KNWIN >= 129 && KW * (KNWIN - 1) < 128, "a cached geometry over a GLV half");
+  static_assert(((uint64_t)KNWIN * (1ull << (KW - 1)) + 1) * BV_ENTRY_U32 ==
+                    (KW == BV_KCW ? BV_KCHALF_U32 : BV_KC18HALF_U32),
+                "the stored half of the cached geometry");
+  const uint32_t h = q / KNWIN;
+  uint32_t kk[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) kk[k] = k12[4 * h + k];
+  return table_leaf<KW, 4>(x, y, zero, tab, kk, (int)(q % KNWIN), (signs >> h) & 1u, h != 0);
 }
 
 // One XYZZ partial sum (+ identity flag) in 33 words (LDS hand-off)

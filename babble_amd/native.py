@@ -38,6 +38,7 @@ EXPORTS = (
     "bv_last_stream", "bv_host_alloc", "bv_host_free", "bv_merge_shard_bits", "bv_plan_group",
     "bv_kc_register", "bv_arena_create", "bv_arena_destroy", "bv_arena_reserve",
     "bv_group_verify_events", "bv_group_kc_register", "bv_plan_event_shards",
+    "bv_kc_small_tables",
 )
 
 
@@ -160,6 +161,8 @@ def lib() -> ctypes.CDLL:
     L.bv_plan_group.restype = ctypes.c_int
     L.bv_kc_register.argtypes = [P, ctypes.c_uint32, P, P]
     L.bv_kc_register.restype = ctypes.c_int
+    L.bv_kc_small_tables.argtypes = [P, ctypes.c_int]
+    L.bv_kc_small_tables.restype = ctypes.c_int
     L.bv_group_verify_events.argtypes = [P, P, ctypes.POINTER(BvResult)]
     L.bv_group_verify_events.restype = ctypes.c_int
     L.bv_group_kc_register.argtypes = [P, ctypes.c_uint32, P, P]

@@ -231,6 +231,12 @@ class Verifier:
         off[1:] = np.cumsum([len(k) for k in pubkeys], dtype=np.uint64)
         self._check(self._L.bv_kc_register(self._ctx, len(pubkeys), buf.ctypes.data, off.ctypes.data))
 
+    def kc_small_tables(self, on: bool = True) -> None:
+        """bv_kc_small_tables: a compact (F_KEY_CACHE | F_KC_COMPACT) context's
+        small batches read its KC18 tables (off after creation).  BvError
+        BV_E_ARGS on any other context."""
+        self._check(self._L.bv_kc_small_tables(self._ctx, 1 if on else 0))
+
     def timing(self) -> dict:
         t = native.BvTiming()
         self._check(self._L.bv_get_timing(self._ctx, ctypes.byref(t)))

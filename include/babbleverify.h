@@ -94,13 +94,20 @@ extern "C" {
                              cached geometry, fixed here.  Admission,
                              registration, eviction and the budget work as
                              above, per 67.1 MB table; bv_timing.key_path
-                             reports 18.  Small batches: the one-launch small
-                             path does not read KC18 tables, so batches of at
-                             most 256 items (env BV_SMALL_MAX) run it as for
-                             keys without a table (key_path 0), the 257-1024
-                             item extension for fully cached batches is off,
-                             and those batches take the bulk pipeline, which
-                             uses the tables (key_path 18).                    */
+                             reports 18.  Small batches: by default the
+                             one-launch small path does not read KC18 tables,
+                             so batches of at most 256 items (env
+                             BV_SMALL_MAX) run it as for keys without a table
+                             (key_path 0), the 257-1024 item extension for
+                             fully cached batches is off, and those batches
+                             take the bulk pipeline, which uses the tables
+                             (key_path 18).  After bv_kc_small_tables(ctx, 1)
+                             the small path reads the KC18 tables as it reads
+                             the 22-bit ones (26 table leaves instead of 22):
+                             a key with a table skips the doubling chain,
+                             fully cached batches of up to 1024 items (env
+                             BV_SMALL_WARM_MAX) take the one launch, and
+                             key_path reports 18 there too.                    */
 #define BV_F_KNOWN (BV_F_KEY_CACHE | BV_F_K8 | BV_F_KC_COMPACT)
 
 typedef struct bv_ctx bv_ctx;
@@ -173,6 +180,20 @@ const char *bv_last_error(const bv_ctx *ctx);
  * batches take the per-batch path), still BV_OK.  bv_get_timing's kc_builds
  * / kc_keys report what was built and what the cache holds. */
 int bv_kc_register(bv_ctx *ctx, uint32_t n_keys, const uint8_t *key_bytes, const uint64_t *key_off);
+
+/* Compact key cache (BV_F_KEY_CACHE | BV_F_KC_COMPACT contexts only): let the
+ * one-launch small-batch path read the context's KC18 tables (on != 0) or
+ * not (on == 0, the state after bv_create).  On: a small batch resolves its
+ * keys against the cache on the host (LRU touch and kc_hits as for 22-bit
+ * tables, never a build); items of a key with a table sum 10 + 2 x 8 table
+ * leaves, items of other keys run the doubling chain in the same launch; a
+ * batch of 257..1024 items (env BV_SMALL_WARM_MAX) takes the small path when
+ * every well-formed key has a table; bv_timing.key_path is 18 when there were
+ * hits.  Off: small batches run as for keys without a table.  Host state
+ * only (no device work); takes effect from the next call.  BV_E_ARGS on a
+ * NULL ctx and on a ctx without BV_F_KC_COMPACT (bv_last_error says so): a
+ * 22-bit context's small path always reads its tables. */
+int bv_kc_small_tables(bv_ctx *ctx, int on);
 
 /* Synchronous batch verify from host buffers (the cgo entry point).  Any
  * input array or result buffer that lies in memory from bv_host_alloc is
