@@ -51,8 +51,57 @@ class PackedBatch:
         return self.key_bytes[self.key_off[k]:self.key_off[k + 1]].tobytes()
 
 
+@dataclass
+class PackedTextBatch:
+    """A PackedBatch without r / s / pre: every item's Signature text instead
+    (bv_text_batch; the library decodes it, on the device for bulk batches)."""
+    msg_bytes: np.ndarray          # u8
+    msg_off: np.ndarray            # u64, n_msgs + 1
+    key_bytes: np.ndarray          # u8
+    key_off: np.ndarray            # u64, n_keys + 1
+    item_msg: np.ndarray           # u32
+    item_key: np.ndarray           # u32
+    sig_off: np.ndarray            # u64, n_items + 1 byte offsets into sig_text
+    sig_text: np.ndarray           # u8: the items' "r|s" texts, concatenated
+
+    @property
+    def n_msgs(self) -> int:
+        return len(self.msg_off) - 1
+
+    @property
+    def n_keys(self) -> int:
+        return len(self.key_off) - 1
+
+    @property
+    def n_items(self) -> int:
+        return len(self.item_msg)
+
+    def signature(self, i: int) -> bytes:
+        return self.sig_text[int(self.sig_off[i]):int(self.sig_off[i + 1])].tobytes()
+
+    def decoded(self) -> PackedBatch:
+        """The PackedBatch of the same items, their texts decoded on the host
+        (bv_decode_signatures)."""
+        pre, r, s = native.decode_signatures(self.sig_off, self.sig_text)
+        return PackedBatch(self.msg_bytes, self.msg_off, self.key_bytes, self.key_off, self.item_msg,
+                           self.item_key, r, s, pre)
+
+
+_ZERO32 = bytes(32)
+
+
+def _cat(chunks):
+    off = np.zeros(len(chunks) + 1, np.uint64)
+    if chunks:
+        off[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(chunks), np.uint8).copy() if chunks else np.zeros(0, np.uint8)
+    return buf, off
+
+
 class BatchBuilder:
-    """Incrementally builds a PackedBatch; keys are de-duplicated by bytes."""
+    """Incrementally builds a PackedBatch (pack) or a PackedTextBatch
+    (pack_text, when every item was added with its text); keys are
+    de-duplicated by bytes."""
 
     def __init__(self):
         self._msgs: List[bytes] = []
@@ -63,6 +112,7 @@ class BatchBuilder:
         self._r: List[bytes] = []
         self._s: List[bytes] = []
         self._pre: List[int] = []
+        self._text: List[Optional[bytes]] = []  # add_item's signature text (None: add_item_raw)
 
     def add_msg(self, body: bytes) -> int:
         self._msgs.append(bytes(body))
@@ -78,9 +128,14 @@ class BatchBuilder:
         return k
 
     def add_item(self, msg: int, key: int, signature) -> int:
-        """signature: the r|s text of EncodeSignature (DecodeSignature semantics)."""
-        pre, r, s = native.decode_signature(signature)
-        return self.add_item_raw(msg, key, pre, r, s)
+        """signature: the r|s text of EncodeSignature (DecodeSignature
+        semantics).  The text is kept as it is: pack() decodes every kept
+        text in ONE bv_decode_signatures call, pack_text() ships them."""
+        if isinstance(signature, str):
+            signature = signature.encode("utf-8")
+        i = self.add_item_raw(msg, key, 0, _ZERO32, _ZERO32)  # (placeholders: pack() decodes the text)
+        self._text[i] = bytes(signature)
+        return i
 
     def add_item_raw(self, msg: int, key: int, pre: int, r_be: bytes, s_be: bytes) -> int:
         self._item_msg.append(msg)
@@ -88,20 +143,30 @@ class BatchBuilder:
         self._pre.append(pre)
         self._r.append(bytes(r_be))
         self._s.append(bytes(s_be))
+        self._text.append(None)
         return len(self._item_msg) - 1
 
     def pack(self) -> PackedBatch:
-        def cat(chunks):
-            off = np.zeros(len(chunks) + 1, np.uint64)
-            if chunks:
-                off[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
-            buf = np.frombuffer(b"".join(chunks), np.uint8).copy() if chunks else np.zeros(0, np.uint8)
-            return buf, off
-
-        mb, mo = cat(self._msgs)
-        kb, ko = cat(self._keys)
+        mb, mo = _cat(self._msgs)
+        kb, ko = _cat(self._keys)
         n = len(self._item_msg)
         r = np.frombuffer(b"".join(self._r), np.uint8).reshape(n, 32).copy() if n else np.zeros((0, 32), np.uint8)
         s = np.frombuffer(b"".join(self._s), np.uint8).reshape(n, 32).copy() if n else np.zeros((0, 32), np.uint8)
+        pre = np.array(self._pre, np.uint8)
+        idx = [i for i, t in enumerate(self._text) if t is not None]
+        if idx:  # add_item's texts, decoded together
+            tb, to = _cat([self._text[i] for i in idx])
+            pre[idx], r[idx], s[idx] = native.decode_signatures(to, tb)
         return PackedBatch(mb, mo, kb, ko, np.array(self._item_msg, np.uint32), np.array(self._item_key, np.uint32),
-                           r, s, np.array(self._pre, np.uint8))
+                           r, s, pre)
+
+    def pack_text(self) -> PackedTextBatch:
+        """The batch with the signature texts add_item was given instead of
+        r / s / pre.  ValueError if an item came through add_item_raw."""
+        if any(t is None for t in self._text):
+            raise ValueError("pack_text: an item was added without its signature text (add_item_raw)")
+        mb, mo = _cat(self._msgs)
+        kb, ko = _cat(self._keys)
+        tb, to = _cat(self._text)
+        return PackedTextBatch(mb, mo, kb, ko, np.array(self._item_msg, np.uint32),
+                               np.array(self._item_key, np.uint32), to, tb)

@@ -318,6 +318,34 @@ int bv_mark_done(bv_ctx *ctx, hipStream_t st) {
   return BV_OK;
 }
 
+// Signature text decoded on the device (bv_internal.h): shared by the item
+// host entry (bv_host_launch, through bv_run_keys) and bv_verify_events.
+int bv_sig_bufs(bv_ctx *ctx, uint64_t n, bv_sig_out *out) {
+  const size_t rs = align256(n * 32);
+  HIPCHK(ctx->d_sig.ensure(2 * rs + align256(n)), BV_E_OOM, "alloc decoded signatures");
+  uint8_t *base = ctx->d_sig.as<uint8_t>();
+  out->r = base, out->s = base + rs, out->pre = base + 2 * rs;
+  return BV_OK;
+}
+
+int bv_sig_decode_launch(bv_ctx *ctx, uint64_t n, const bv_sig_text &d_sig, const bv_sig_out &out,
+                         uint64_t text_base) {
+  // (a shard's text: the offsets are the whole batch's, the text starts at byte text_base)
+  HIPCHK(text_base ? bvk::sig_decode_rb(ctx->sstream, n, d_sig.off, d_sig.text, text_base, out.r, out.s, out.pre)
+                   : bvk::sig_decode(ctx->sstream, n, d_sig.off, d_sig.text, out.r, out.s, out.pre),
+         BV_E_LAUNCH, "k_sig_decode");
+  HIPCHK(hipEventRecord(ctx->S().ev[E_SDEC], ctx->sstream), BV_E_LAUNCH, "event");
+  return BV_OK;
+}
+
+int bv_sig_decode_on_device(bv_ctx *ctx, uint64_t n, const uint64_t *d_off, const uint8_t *d_text,
+                            hipEvent_t text_ready, bv_sig_out *out, uint64_t text_base) {
+  const int rc = bv_sig_bufs(ctx, n, out);
+  if (rc != BV_OK) return rc;
+  HIPCHK(hipStreamWaitEvent(ctx->sstream, text_ready, 0), BV_E_LAUNCH, "join signature text");
+  return bv_sig_decode_launch(ctx, n, bv_sig_text{d_off, d_text}, *out, text_base);
+}
+
 static const uint8_t kGenerator[64] = {
     0x79, 0xBE, 0x66, 0x7E, 0xF9, 0xDC, 0xBB, 0xAC, 0x55, 0xA0, 0x62, 0x95, 0xCE, 0x87, 0x0B, 0x07,
     0x02, 0x9B, 0xFC, 0xDB, 0x2D, 0xCE, 0x28, 0xD9, 0x59, 0xF2, 0x81, 0x5B, 0x16, 0xF8, 0x17, 0x98,
@@ -612,7 +640,8 @@ extern "C" int bv_get_timing(const bv_ctx *ctx, bv_timing *out) {
 // `keys_ready` (the keys in HBM).  The host entry points stage the keys
 // first, then s and pre, so the key tables build while the rest of the batch
 // still crosses PCIe.
-int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_t s_ready, bool kc, bool split_ok) {
+int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_t s_ready, bool kc, bool split_ok,
+                const bv_sig_text *d_sig) {
   const uint64_t n_items = b->n_items;
   const uint32_t n_keys = b->n_keys;
   if (n_items > 0 && (!b->item_msg || !b->item_key || !b->r_be || !b->s_be))
@@ -669,6 +698,11 @@ int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_
   HIPCHK(hipEventRecord(ev[E_KDEC], ctx->sstream), BV_E_LAUNCH, "event");
   // s^-1 needs only s: concurrent with everything up to k_verify_g
   HIPCHK(hipStreamWaitEvent(ctx->sstream, s_ready, 0), BV_E_LAUNCH, "fork");
+  if (d_sig) {  // signature text: r, s and pre (b's arrays, in ctx->d_sig) are decoded from it first
+    const int rc = bv_sig_decode_launch(ctx, n_items, *d_sig, bv_sig_out{(uint8_t *)b->r_be, (uint8_t *)b->s_be,
+                                                                        (uint8_t *)b->pre});
+    if (rc != BV_OK) return rc;
+  }
   // items per lane: kPrepM amortises the inversion in large batches; a small
   // batch spreads over ~64k lanes instead, since there the serial chain of
   // one lane (M products, the inversion, 2M products) is the latency
@@ -958,11 +992,11 @@ extern "C" int bv_sync(bv_ctx *ctx) {
 // ---------------------------------------------------------------------------
 // host entry point
 // ---------------------------------------------------------------------------
-int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b) {
+int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b, bool text) {
   const uint64_t n_msgs = b->n_msgs, n_items = b->n_items;
   const uint32_t n_keys = b->n_keys;
   if ((n_msgs && !b->msg_off) || (n_keys && !b->key_off) ||
-      (n_items && (!b->item_msg || !b->item_key || !b->r_be || !b->s_be)))
+      (n_items && (!b->item_msg || !b->item_key || (!text && (!b->r_be || !b->s_be)))))
     return bv_fail(ctx, BV_E_ARGS, "null input array");
   if (n_items && !n_keys) return bv_fail(ctx, BV_E_ARGS, "items without keys");
   const uint64_t msg_len = n_msgs ? b->msg_off[n_msgs] : 0;
@@ -995,10 +1029,11 @@ int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b) {
 // Stage a host batch into HBM (pinned chunks on the copy stream), hash the
 // messages chunk by chunk as they land and launch the verify pipeline.
 // Returns with the work enqueued; bv_host_finish waits and copies results.
-int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res) {
+int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res,
+                   const bv_sig_text *sig) {
   const auto t0 = std::chrono::steady_clock::now();
   call->t0 = t0;
-  int rc = bv_validate_host_batch(ctx, b);
+  int rc = bv_validate_host_batch(ctx, b, sig != nullptr);
   if (rc != BV_OK) return rc;
   // BV_HOST_STAMPS (diagnostics): the host phases of this call on stderr
   auto stamp_ms = [t0]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -1035,15 +1070,22 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
     total += align256(n + pad);
   };
   // staging order: the keys (the key tables start once they land), s and
-  // pre (s^-1), the other item arrays, then the message bytes
+  // pre (s^-1), the other item arrays, then the message bytes.  With
+  // signature text its offsets and bytes take the place of s and pre (the
+  // s^-1 stream decodes r, s and pre from them), and r is not staged.
   add(1, b->key_off, n_keys ? (n_keys + 1) * 8ull : 0, 0);
   add(2, b->key_bytes, key_len, 64);
-  add(6, b->s_be, n_items * 32, 0);
-  add(7, b->pre, b->pre ? n_items : 0, 0);
+  if (sig) {
+    add(6, sig->off, (n_items + 1) * 8, 0);
+    add(7, sig->text, sig->off[n_items], 0);
+  } else {
+    add(6, b->s_be, n_items * 32, 0);
+    add(7, b->pre, b->pre ? n_items : 0, 0);
+  }
   add(0, b->msg_off, n_msgs ? (n_msgs + 1) * 8 : 0, 0);
   add(3, b->item_msg, n_items * 4, 0);
   add(4, b->item_key, n_items * 4, 0);
-  add(5, b->r_be, n_items * 32, 0);
+  add(5, b->r_be, sig ? 0 : n_items * 32, 0);
   add(8, b->msg_bytes, msg_len, 64);
   // previous work on this ctx must be done before its staging is reused
   if (bv_wait_all(ctx) != BV_OK) return BV_E_LAUNCH;  // previous calls' work buffers / staging
@@ -1135,6 +1177,15 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
   d.r_be = dev + segs[5].off;
   d.s_be = dev + segs[6].off;
   d.pre = b->pre ? dev + segs[7].off : nullptr;
+  bv_sig_text dsig;
+  if (sig) {  // decoded on the s^-1 stream (bv_run_keys) into ctx->d_sig
+    dsig.off = (const uint64_t *)(dev + segs[6].off);
+    dsig.text = dev + segs[7].off;
+    bv_sig_out so;
+    rc = bv_sig_bufs(ctx, n_items, &so);
+    if (rc != BV_OK) return rc;
+    d.r_be = so.r, d.s_be = so.s, d.pre = so.pre;
+  }
 
   if (ctx->host_stamps) st_items = stamp_ms();
   // key cache resolution needs the keys on the device (decode of misses)
@@ -1149,8 +1200,10 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
   }
   // the key tables need only the keys and s^-1 only s: they run while the
   // rest of the batch still crosses PCIe
-  rc = bv_run_keys(ctx, &d, ctx->S().ev[E_KREADY], ctx->S().ev[E_SREADY], kc);
+  rc = bv_run_keys(ctx, &d, ctx->S().ev[E_KREADY], ctx->S().ev[E_SREADY], kc, false, sig ? &dsig : nullptr);
   if (rc != BV_OK) return rc;
+  // (the verify kernels on `st` read the decoded arrays; they are also behind s^-1, which is behind the decode)
+  if (sig) HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");
 
   // Items in message order (item_msg non-decreasing: events, blocks) are
   // verified chunk by chunk as their messages are hashed, so the verify
@@ -1362,7 +1415,7 @@ constexpr uint8_t kSmallPending = 0xFF;      // status sentinel (statuses are 0.
 // cold path that measured 0.32 / 0.40 ms at 256 / 512 items gave a false
 // REJECT on ~1 in 3000 items of a process's first batch and was withdrawn
 // (DESIGN.md section 4, round 5).
-static bool small_batch(bv_ctx *ctx, const bv_batch *b) {
+static bool small_batch(bv_ctx *ctx, const bv_batch *b, bool text = false) {
   if (b->n_items == 0) return false;
   const uint64_t n = std::max<uint64_t>(b->n_items, b->n_msgs);
   if (n > ctx->small_max) {
@@ -1370,7 +1423,7 @@ static bool small_batch(bv_ctx *ctx, const bv_batch *b) {
       return false;
     // the key bytes are read below: only a well-formed batch (the bulk path
     // reports a malformed one through its own validation)
-    if (bv_validate_host_batch(ctx, b) != BV_OK || !bv_kc_all_cached(ctx, b->n_keys, b->key_bytes, b->key_off))
+    if (bv_validate_host_batch(ctx, b, text) != BV_OK || !bv_kc_all_cached(ctx, b->n_keys, b->key_bytes, b->key_off))
       return false;
   }
   if (b->n_msgs && !b->msg_off) return false;  // (validation reports it)
@@ -1379,7 +1432,11 @@ static bool small_batch(bv_ctx *ctx, const bv_batch *b) {
   return true;
 }
 
-static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
+// `sig` (may be null; validated by the caller): the items' signature text.
+// The host parser (bv_decode_signature) writes r, s and pre straight into
+// the mapped buffer, so k_small and the host item records see what they see
+// for a bv_verify_batch call over the decoded arrays.
+static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res, const bv_sig_text *sig = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
   const uint64_t n_msgs = b->n_msgs, n_items = b->n_items;
   const uint32_t n_keys = b->n_keys;
@@ -1431,9 +1488,25 @@ static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
   put(o_koff, b->key_off, (n_keys + 1) * 8ull);
   put(o_im, b->item_msg, n_items * 4);
   put(o_ik, b->item_key, n_items * 4);
-  put(o_r, b->r_be, n_items * 32);
-  put(o_s, b->s_be, n_items * 32);
-  if (b->pre) put(o_pre, b->pre, n_items);
+  // r, s and pre as the kernel and the records read them: the caller's
+  // arrays, or with signature text the mapped buffer the parser fills
+  const uint8_t *r_src = b->r_be, *s_src = b->s_be, *pre_src = b->pre;
+  if (sig) {
+    uint8_t *pr = pin + o_r, *ps = pin + o_s, *pp = pin + o_pre;
+    auto parse = [sig, pr, ps, pp](uint64_t lo, uint64_t hi) {
+      for (uint64_t i = lo; i < hi; i++)
+        pp[i] = bv_decode_signature((const char *)sig->text + sig->off[i], sig->off[i + 1] - sig->off[i], pr + 32 * i,
+                                    ps + 32 * i);
+      return true;
+    };
+    if (n_items <= 16) parse(0, n_items);
+    else ctx->pool->parallel_for(n_items, 16, parse);
+    r_src = pr, s_src = ps, pre_src = pp;
+  } else {
+    put(o_r, b->r_be, n_items * 32);
+    put(o_s, b->s_be, n_items * 32);
+    if (b->pre) put(o_pre, b->pre, n_items);
+  }
   // statuses start as a sentinel no status takes: the host sees each one
   // land in this (coherent) buffer and returns without waiting for the
   // kernel's completion signal
@@ -1458,8 +1531,8 @@ static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
     it.resize(n_items);
     for (uint64_t i = 0; i < n_items; i++) {
       const uint32_t k = b->item_key[i];
-      it[i] = {dig + 32ull * b->item_msg[i], b->r_be + 32 * i, b->s_be + 32 * i, b->key_bytes + b->key_off[k],
-               b->key_off[k + 1] - b->key_off[k], kc ? tabs[k] : 0, (uint8_t)(b->pre ? b->pre[i] : 0)};
+      it[i] = {dig + 32ull * b->item_msg[i], r_src + 32 * i, s_src + 32 * i, b->key_bytes + b->key_off[k],
+               b->key_off[k + 1] - b->key_off[k], kc ? tabs[k] : 0, (uint8_t)(pre_src ? pre_src[i] : 0)};
     }
     uint32_t *rp = (uint32_t *)(pin + o_rec);
     ctx->pool->parallel_for(n_items, kHostRecGrain, [&](uint64_t lo, uint64_t hi) {
@@ -1476,7 +1549,7 @@ static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
   }
   HIPCHK(bvk::verify_small(st, ctx->kc_w, (uint32_t)n_items, dev + o_dig, dev + o_key, (const uint64_t *)(dev + o_koff),
                            (const uint32_t *)(dev + o_im), (const uint32_t *)(dev + o_ik), dev + o_r, dev + o_s,
-                           b->pre ? dev + o_pre : nullptr, kc ? (const uint64_t *)(dev + o_tab) : nullptr,
+                           pre_src ? dev + o_pre : nullptr, kc ? (const uint64_t *)(dev + o_tab) : nullptr,
                            ctx->g_table, dev + o_st, stamps, recs ? (const uint32_t *)(dev + o_rec) : nullptr,
                            (uint64_t *)(dev + o_clk)),
          BV_E_LAUNCH, "k_small");
@@ -1552,6 +1625,44 @@ extern "C" int bv_verify_batch(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
   int rc = bv_host_launch(ctx, b, &call, res);
   if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
   return bv_host_finish(ctx, b, res, &call, true);
+}
+
+// The signature text of an item batch (bv_verify_batch_text): offsets from 0,
+// monotone (checked on the pool), bytes present when any text is non-empty.
+static int validate_sig_text(bv_ctx *ctx, uint64_t n_items, const bv_sig_text &sig) {
+  if (!sig.off) return bv_fail(ctx, BV_E_ARGS, "null sig_off");
+  if (sig.off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "sig_off[0] != 0");
+  const uint64_t *off = sig.off;
+  if (!ctx->pool->parallel_for(n_items, 1 << 17, [off](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++)
+          if (off[i] > off[i + 1]) return false;
+        return true;
+      }))
+    return bv_fail(ctx, BV_E_ARGS, "sig_off not monotone");
+  if (off[n_items] && !sig.text) return bv_fail(ctx, BV_E_ARGS, "null sig_text");
+  return BV_OK;
+}
+
+extern "C" int bv_verify_batch_text(bv_ctx *ctx, const bv_text_batch *tb, bv_result *res) {
+  if (!ctx || !tb || !res) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
+  bv_batch b = tb->items;  // r_be, s_be and pre are ignored
+  b.r_be = b.s_be = b.pre = nullptr;
+  // (no items: no text either; the messages are hashed as by bv_verify_batch)
+  const bv_sig_text text{tb->sig_off, tb->sig_text}, *sig = b.n_items ? &text : nullptr;
+  int rc = sig ? validate_sig_text(ctx, b.n_items, text) : BV_OK;
+  if (rc != BV_OK) return rc;
+  if (ctx->small_path && small_batch(ctx, &b, sig != nullptr)) {
+    rc = bv_validate_host_batch(ctx, &b, sig != nullptr);
+    if (rc != BV_OK) return rc;
+    rc = small_verify(ctx, &b, res, sig);
+    return rc == BV_OK ? rc : bv_drain(ctx, ctx->stream, rc);
+  }
+  bv_host_call call;
+  rc = bv_host_launch(ctx, &b, &call, res, sig);
+  if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
+  return bv_host_finish(ctx, &b, res, &call, true);
 }
 
 extern "C" int bv_sha256_batch(bv_ctx *ctx, uint64_t n_msgs, const uint8_t *msg_bytes, const uint64_t *msg_off,

@@ -95,27 +95,6 @@ int validate(bv_ctx *ctx, const bv_event_batch *b) {
   return BV_OK;
 }
 
-// Signature text (eb->sig_text): the device decodes r, s and pre into
-// ctx->d_sig on the s^-1 stream once the text has landed (`text_ready`),
-// ahead of s^-1; E_SDEC marks them written.  Returns the device arrays.
-struct SigOut {
-  uint8_t *r = nullptr, *s = nullptr, *pre = nullptr;
-};
-int sig_decode_on_device(bv_ctx *ctx, uint64_t n, const uint64_t *d_off, const uint8_t *d_text, hipEvent_t text_ready,
-                         SigOut *out, uint64_t text_base = 0) {
-  const size_t rs = align256(n * 32);
-  HIPCHK(ctx->d_sig.ensure(2 * rs + align256(n)), BV_E_OOM, "alloc decoded signatures");
-  uint8_t *base = ctx->d_sig.as<uint8_t>();
-  out->r = base, out->s = base + rs, out->pre = base + 2 * rs;
-  HIPCHK(hipStreamWaitEvent(ctx->sstream, text_ready, 0), BV_E_LAUNCH, "join signature text");
-  // (a shard's text: the offsets are the whole batch's, the text starts at byte text_base)
-  HIPCHK(text_base ? bvk::sig_decode_rb(ctx->sstream, n, d_off, d_text, text_base, out->r, out->s, out->pre)
-                   : bvk::sig_decode(ctx->sstream, n, d_off, d_text, out->r, out->s, out->pre),
-         BV_E_LAUNCH, "k_sig_decode");
-  HIPCHK(hipEventRecord(ctx->S().ev[E_SDEC], ctx->sstream), BV_E_LAUNCH, "event");
-  return BV_OK;
-}
-
 }  // namespace
 
 int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb) { return validate(ctx, eb); }
@@ -198,8 +177,8 @@ static int verify_events_dag_host(bv_ctx *ctx, const bv_event_batch *eb, bv_resu
   if ((rc = h2d(keys_end, s_end)) != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_SREADY], cs), BV_E_LAUNCH, "event");
   if (text) {
-    SigOut so;
-    rc = sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so);
+    bv_sig_out so;
+    rc = bv_sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so);
     if (rc != BV_OK) return rc;
     vb.r_be = so.r, vb.s_be = so.s, vb.pre = so.pre;
   }
@@ -583,9 +562,9 @@ int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_SREADY], cs), BV_E_LAUNCH, "event");
   if (text) {  // r, s, pre from the text, ahead of s^-1; the verify stream reads them
-    SigOut so;
-    rc = sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so,
-                              sig_base);
+    bv_sig_out so;
+    rc = bv_sig_decode_on_device(ctx, n, (const uint64_t *)(dev + o_s), dev + o_pre, ctx->S().ev[E_SREADY], &so,
+                                 sig_base);
     if (rc != BV_OK) return rc;
     vb.r_be = d.r_be = so.r, vb.s_be = d.s_be = so.s, vb.pre = d.pre = so.pre;
     HIPCHK(hipStreamWaitEvent(vst, ctx->S().ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");

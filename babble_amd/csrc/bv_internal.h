@@ -263,7 +263,7 @@ struct bv_ctx {
   double wall_khz = 1e5;  // the device's constant clock (hipDeviceAttributeWallClockRate)
   DevBuf d_in;
   DevBuf d_stamps;  // BV_SMALL_STAMPS: k_small phase clocks (diagnostics)
-  DevBuf d_sig;     // bv_verify_events with signature text: the decoded r, s, pre
+  DevBuf d_sig;     // host entries with signature text: the decoded r, s, pre (bv_sig_bufs)
   // host entry: messages longer than kHostHashLen hashed on the host (their
   // index and digest), uploaded beside the device hashing
   PinnedBuf pin_long;
@@ -381,13 +381,38 @@ hipError_t bv_host_wait(bv_ctx *ctx, hipStream_t st);
 // Next slot for a device call writing `res`: st waits for the slot's last
 // call, and for the other slot's last call when their result ranges overlap.
 int bv_slot_begin(bv_ctx *ctx, hipStream_t st, const bv_batch *b, const bv_result *res);  // record the end of this call (its slot and ev_done)
-int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b);
+// text: the items' r / s / pre come from signature text (bv_sig_text): r_be / s_be may be null
+int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b, bool text = false);
+// Signature text of a host-entry call (bv_verify_batch_text; bv_verify_events
+// with sig_text): item i's "r|s" is text[off[i] .. off[i+1]).  Host pointers
+// for bv_host_launch, device pointers for bv_run_keys.
+struct bv_sig_text {
+  const uint64_t *off = nullptr;
+  const uint8_t *text = nullptr;
+};
+// The decoded r, s and pre of n signatures in ctx->d_sig (device arrays).
+struct bv_sig_out {
+  uint8_t *r = nullptr, *s = nullptr, *pre = nullptr;
+};
+int bv_sig_bufs(bv_ctx *ctx, uint64_t n, bv_sig_out *out);  // (re)allocates ctx->d_sig for n signatures
+// k_sig_decode on the s^-1 stream into `out` (bv_sig_bufs), then E_SDEC.  The
+// caller has ordered the s^-1 stream after the text's arrival.  text_base: a
+// shard's text (the offsets are the whole batch's, the text starts there).
+int bv_sig_decode_launch(bv_ctx *ctx, uint64_t n, const bv_sig_text &d_sig, const bv_sig_out &out,
+                         uint64_t text_base = 0);
+// Both, after `text_ready` (the text in HBM), ahead of s^-1: the s^-1 stream
+// decodes r, s and pre into ctx->d_sig; E_SDEC marks them written.
+int bv_sig_decode_on_device(bv_ctx *ctx, uint64_t n, const uint64_t *d_off, const uint8_t *d_text,
+                            hipEvent_t text_ready, bv_sig_out *out, uint64_t text_base = 0);
 int bv_run_device(bv_ctx *ctx, const bv_batch *b, uint8_t *d_msg_hash, uint8_t *d_status, uint64_t *d_bits,
                   hipStream_t st, bool hashed, bool kc);
 // split_ok: r is in HBM by s_ready too, so u2's GLV split may run on the
 // s^-1 stream (k_glv_split) instead of in k_verify_g (the device entry)
+// d_sig (device pointers; s_ready then marks the text in HBM): b's r_be / s_be
+// / pre are the arrays of bv_sig_bufs and are decoded from the text on the
+// s^-1 stream after the key decode, right before k_sinv
 int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_t s_ready, bool kc,
-                bool split_ok = false);
+                bool split_ok = false, const bv_sig_text *d_sig = nullptr);
 struct bv_out {  // device outputs of one verify
   uint32_t *dig = nullptr;
   uint8_t *status = nullptr;
@@ -438,7 +463,11 @@ void bv_kc_init(bv_ctx *ctx);     // budget, admission and fault-injection setti
 void bv_kc_release(bv_ctx *ctx);  // free every cached table (bv_destroy, after all calls finished)
 // `res` (may be null): the caller's result buffers, written by DMA directly
 // when they are bv_host_alloc memory (else bv_host_finish copies them).
-int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res = nullptr);
+// `sig` (may be null; host pointers, validated by the caller): the items'
+// signature text, staged where s and pre are otherwise and decoded on the
+// device; b's r_be / s_be / pre are then neither read nor staged.
+int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res = nullptr,
+                   const bv_sig_text *sig = nullptr);
 int bv_host_finish(bv_ctx *ctx, const bv_batch *b, bv_result *res, bv_host_call *call, bool bits_out);
 // bv_verify_events' bulk path over one event range of a batch (bv_events.cpp):
 // events [a, z) and the parent hashes [hash_lo, hash_hi) its BV_PARENT_HASH

@@ -127,6 +127,21 @@ extern "C" uint8_t bv_decode_signature(const char *sig, size_t len, uint8_t r_be
   return BV_PRE(rc, sc);
 }
 
+extern "C" int bv_decode_signatures(uint64_t n, const uint64_t *sig_off, const uint8_t *sig_text, uint8_t *r_be,
+                                    uint8_t *s_be, uint8_t *pre) {
+  if (n == 0) return BV_OK;
+  if (!sig_off || !r_be || !s_be || !pre) return BV_E_ARGS;
+  for (uint64_t i = 0; i < n; i++)
+    if (sig_off[i] > sig_off[i + 1]) return BV_E_ARGS;
+  if (!sig_text && sig_off[n] > sig_off[0]) return BV_E_ARGS;
+  static const char kEmpty[1] = {0};
+  for (uint64_t i = 0; i < n; i++) {
+    const size_t len = (size_t)(sig_off[i + 1] - sig_off[i]);
+    pre[i] = bv_decode_signature(len ? (const char *)sig_text + sig_off[i] : kEmpty, len, r_be + 32 * i, s_be + 32 * i);
+  }
+  return BV_OK;
+}
+
 extern "C" int64_t bv_hex_decode(const char *s, size_t len, uint8_t *out) {
   if (len < 2) return -1;
   const char *src = s + 2;

@@ -306,10 +306,18 @@ def _add_itx(bb: BatchBuilder, itx: InternalTransaction) -> Optional[int]:
     return bb.add_item(m, bb.add_key(pub), itx.Signature)
 
 
-def verify_itxs(itxs: Sequence[InternalTransaction], verifier=None) -> List[Outcome]:
+def _verify_items(bb: BatchBuilder, verifier, text: bool):
+    """The builder's items through bv_verify_batch, or with text=True through
+    bv_verify_batch_text (the signature texts shipped as they are and decoded
+    by the library instead of one bv_decode_signature call per item)."""
+    v = verifier or default_verifier()
+    return v.verify_text(bb.pack_text()) if text else v.verify(bb.pack())
+
+
+def verify_itxs(itxs: Sequence[InternalTransaction], verifier=None, text: bool = False) -> List[Outcome]:
     bb = BatchBuilder()
     idx = [_add_itx(bb, t) for t in itxs]
-    res = (verifier or default_verifier()).verify(bb.pack()) if bb._item_msg else None
+    res = _verify_items(bb, verifier, text) if bb._item_msg else None
     out = []
     for t, k in zip(itxs, idx):
         if k is None:
@@ -356,15 +364,17 @@ def compose_event_outcome(itx_statuses: Sequence[Optional[int]], event_status: i
     return _item_outcome(event_status, event_sig)
 
 
-def verify_block_signatures(block: Block, sigs: Sequence[BlockSignature], verifier=None) -> List[Outcome]:
+def verify_block_signatures(block: Block, sigs: Sequence[BlockSignature], verifier=None,
+                            text: bool = False) -> List[Outcome]:
     """Block.Verify for every signature: the body is hashed once, not per
-    signature (block.go:344 re-hashes on every call)."""
+    signature (block.go:344 re-hashes on every call).  text=True: the
+    signature texts go to the library undecoded (bv_verify_batch_text)."""
     if not sigs:
         return []
     bb = BatchBuilder()
     m = bb.add_msg(block.Body.Marshal())
     items = [bb.add_item(m, bb.add_key(s.Validator or b""), s.Signature) for s in sigs]
-    res = (verifier or default_verifier()).verify(bb.pack())
+    res = _verify_items(bb, verifier, text)
     return [_item_outcome(int(res.status[k]), s.Signature) for s, k in zip(sigs, items)]
 
 
@@ -387,11 +397,12 @@ def check_block(block: Block, peer_set: PeerSet, verifier=None) -> Optional[str]
 
 
 def process_sig_pool(pending: Sequence[BlockSignature], get_block: Callable[[int], Optional[Block]],
-                     get_peer_set: Callable[[int], Optional[PeerSet]], verifier=None):
+                     get_peer_set: Callable[[int], Optional[PeerSet]], verifier=None, text: bool = False):
     """Hashgraph.ProcessSigPool (hashgraph.go:1295-1367) over `pending` in the
     given (map) order.  Returns (appended signatures, error or None); a
     DecodeSignature error aborts the pool at that signature, as in Go.
-    All candidate signatures are verified in one device batch first."""
+    All candidate signatures are verified in one device batch first
+    (text=True: from their texts, bv_verify_batch_text)."""
     cands = []
     for bs in pending:
         blk = get_block(bs.Index)
@@ -408,7 +419,7 @@ def process_sig_pool(pending: Sequence[BlockSignature], get_block: Callable[[int
         if id(blk) not in msg_of:
             msg_of[id(blk)] = bb.add_msg(blk.Body.Marshal())
         items.append(bb.add_item(msg_of[id(blk)], bb.add_key(bs.Validator or b""), bs.Signature))
-    res = (verifier or default_verifier()).verify(bb.pack()) if items else None
+    res = _verify_items(bb, verifier, text) if items else None
     appended = []
     for (bs, blk), k in zip(cands, items):
         o = _item_outcome(int(res.status[k]), bs.Signature)

@@ -38,7 +38,7 @@ EXPORTS = (
     "bv_last_stream", "bv_host_alloc", "bv_host_free", "bv_merge_shard_bits", "bv_plan_group",
     "bv_kc_register", "bv_arena_create", "bv_arena_destroy", "bv_arena_reserve",
     "bv_group_verify_events", "bv_group_kc_register", "bv_plan_event_shards",
-    "bv_kc_small_tables",
+    "bv_kc_small_tables", "bv_verify_batch_text", "bv_decode_signatures",
 )
 
 
@@ -56,6 +56,14 @@ class BvBatch(ctypes.Structure):
         ("r_be", ctypes.c_void_p),
         ("s_be", ctypes.c_void_p),
         ("pre", ctypes.c_void_p),
+    ]
+
+
+class BvTextBatch(ctypes.Structure):
+    _fields_ = [
+        ("items", BvBatch),
+        ("sig_off", ctypes.c_void_p),
+        ("sig_text", ctypes.c_void_p),
     ]
 
 
@@ -122,6 +130,10 @@ def lib() -> ctypes.CDLL:
     L.bv_last_error.restype = ctypes.c_char_p
     L.bv_verify_batch.argtypes = [P, ctypes.POINTER(BvBatch), ctypes.POINTER(BvResult)]
     L.bv_verify_batch.restype = ctypes.c_int
+    L.bv_verify_batch_text.argtypes = [P, ctypes.POINTER(BvTextBatch), ctypes.POINTER(BvResult)]
+    L.bv_verify_batch_text.restype = ctypes.c_int
+    L.bv_decode_signatures.argtypes = [ctypes.c_uint64, P, P, P, P, P]
+    L.bv_decode_signatures.restype = ctypes.c_int
     L.bv_verify_batch_device.argtypes = [P, ctypes.POINTER(BvBatch), ctypes.POINTER(BvResult), P, ctypes.c_int]
     L.bv_verify_batch_device.restype = ctypes.c_int
     L.bv_sha256_batch.argtypes = [P, ctypes.c_uint64, P, P, P]
@@ -190,6 +202,27 @@ def decode_signature(sig: bytes):
     s = ctypes.create_string_buffer(32)
     pre = lib().bv_decode_signature(sig, len(sig), r, s)
     return pre, r.raw, s.raw
+
+
+def decode_signatures(sig_off, sig_text):
+    """bv_decode_signatures: bv_decode_signature over len(sig_off) - 1 texts in
+    one call -> (pre [n] u8, r_be [n, 32] u8, s_be [n, 32] u8)."""
+    import numpy as np
+
+    off = np.ascontiguousarray(sig_off, dtype=np.uint64)
+    text = np.ascontiguousarray(sig_text, dtype=np.uint8)
+    n = max(len(off) - 1, 0)
+    if n and int(off[n]) > text.size:
+        raise BvError(BV_E_ARGS, "sig_off runs past sig_text")
+    r = np.zeros((n, 32), np.uint8)
+    s = np.zeros((n, 32), np.uint8)
+    pre = np.zeros(n, np.uint8)
+    rc = lib().bv_decode_signatures(n, off.ctypes.data if n else None, text.ctypes.data if text.size else None,
+                                    r.ctypes.data if n else None, s.ctypes.data if n else None,
+                                    pre.ctypes.data if n else None)
+    if rc != BV_OK:
+        raise BvError(rc, "bv_decode_signatures")
+    return pre, r, s
 
 
 class ReferencePanic(Exception):

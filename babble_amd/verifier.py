@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import native
-from .batch import PackedBatch
+from .batch import PackedBatch, PackedTextBatch
 
 
 @dataclass
@@ -170,6 +170,26 @@ class Verifier:
         self._check(self._L.bv_verify_batch(self._ctx, ctypes.byref(cb), ctypes.byref(r)))
         return res
 
+    def verify_text(self, tb: PackedTextBatch) -> VerifyResult:
+        """bv_verify_batch_text: the items' signatures as Go text, decoded by
+        the library (on the device for bulk batches).  Results equal verify()
+        over tb.decoded()."""
+        nm, ni, nw = max(tb.n_msgs, 1), max(tb.n_items, 1), max((tb.n_items + 63) // 64, 1)
+        res = VerifyResult(np.empty((nm, 32), np.uint8), np.empty(ni, np.uint8), np.empty(nw, np.uint64))
+        self.verify_text_into(tb, res)
+        return VerifyResult(res.msg_hash[: tb.n_msgs], res.status[: tb.n_items],
+                            res.accept_bits[: (tb.n_items + 63) // 64])
+
+    def verify_text_into(self, tb: PackedTextBatch, res: VerifyResult) -> VerifyResult:
+        """bv_verify_batch_text into caller-owned result arrays (PinnedArena
+        arrays are reached by DMA; so are the inputs of a batch built by
+        PinnedArena.text_batch)."""
+        keep: list = []
+        ctb = _ctbatch(tb, keep)
+        r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
+        self._check(self._L.bv_verify_batch_text(self._ctx, ctypes.byref(ctb), ctypes.byref(r)))
+        return res
+
     def sync(self) -> None:
         """bv_sync: wait for this ctx's last (async) call."""
         self._check(self._L.bv_sync(self._ctx))
@@ -292,6 +312,33 @@ def _cbatch(b: PackedBatch, keep: list) -> "native.BvBatch":
         except AttributeError:  # (a batch type without a __dict__: no cache)
             pass
     return cb
+
+
+def _ctbatch(tb: PackedTextBatch, keep: list) -> "native.BvTextBatch":
+    """The bv_text_batch of `tb` (arrays converted to the C dtypes, contiguous;
+    r_be / s_be / pre stay NULL)."""
+    conv = []
+
+    def c(a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        conv.append(a)
+        return a
+
+    ctb = native.BvTextBatch()
+    cb = ctb.items
+    cb.n_msgs = tb.n_msgs
+    cb.msg_bytes = _p(c(tb.msg_bytes, np.uint8))
+    cb.msg_off = _p(c(tb.msg_off, np.uint64))
+    cb.n_keys = tb.n_keys
+    cb.key_bytes = _p(c(tb.key_bytes, np.uint8))
+    cb.key_off = _p(c(tb.key_off, np.uint64))
+    cb.n_items = tb.n_items
+    cb.item_msg = _p(c(tb.item_msg, np.uint32))
+    cb.item_key = _p(c(tb.item_key, np.uint32))
+    ctb.sig_off = _p(c(tb.sig_off, np.uint64))
+    ctb.sig_text = _p(c(tb.sig_text, np.uint8))
+    keep.append(conv)
+    return ctb
 
 
 def plan_shards(b: PackedBatch, n_shards: int) -> np.ndarray:
@@ -472,6 +519,13 @@ class PinnedArena:
                            self.copy(b.key_off.astype(np.uint64)), self.copy(b.item_msg.astype(np.uint32)),
                            self.copy(b.item_key.astype(np.uint32)), self.copy(b.r_be), self.copy(b.s_be),
                            None if b.pre is None else self.copy(b.pre))
+
+    def text_batch(self, tb: PackedTextBatch) -> PackedTextBatch:
+        """The same text batch with every array in pinned memory."""
+        return PackedTextBatch(self.copy(tb.msg_bytes), self.copy(tb.msg_off.astype(np.uint64)),
+                               self.copy(tb.key_bytes), self.copy(tb.key_off.astype(np.uint64)),
+                               self.copy(tb.item_msg.astype(np.uint32)), self.copy(tb.item_key.astype(np.uint32)),
+                               self.copy(tb.sig_off.astype(np.uint64)), self.copy(tb.sig_text))
 
     def wire(self, eb):
         """The same events.EventWireBatch with every array in pinned memory

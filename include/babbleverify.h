@@ -12,6 +12,9 @@
  *                     as composed by Event.Verify             src/hashgraph/event.go:219-247
  *                     InternalTransaction.Verify              src/hashgraph/internal_transaction.go:139-154
  *                     Block.Verify                            src/hashgraph/block.go:343-357
+ *   bv_verify_batch_text  the same items from their Signature text:
+ *                     keys.DecodeSignature applied by the library
+ *                                                             src/crypto/keys/signature.go:31-39
  *   bv_sha256_batch   N x crypto.SHA256                       src/crypto/hash.go:8-13
  *   bv_decode_signature  keys.DecodeSignature + the sign/range
  *                     pre-checks of ecdsa.Verify              src/crypto/keys/signature.go:31-39
@@ -200,6 +203,32 @@ int bv_kc_small_tables(bv_ctx *ctx, int on);
  * moved by DMA from / to where it is; other (pageable) buffers go through
  * the ctx's pinned staging, one extra host copy each. */
 int bv_verify_batch(bv_ctx *ctx, const bv_batch *batch, bv_result *result);
+
+/* bv_verify_batch for callers that hold each item's signature as Go text:
+ * Block.Verify over BlockSignature.Signature (src/hashgraph/block.go:343-357),
+ * InternalTransaction.Verify (internal_transaction.go:139-154),
+ * ProcessSigPool and processJoinRequest.  Instead of one bv_decode_signature
+ * call per item the caller appends each "r|s" string's bytes to sig_text and
+ * an offset to sig_off; the library decodes every text as
+ * bv_decode_signature does (keys.DecodeSignature + the range checks,
+ * src/crypto/keys/signature.go:31-39).  A batch that takes the bulk pipeline
+ * ships the text instead of r / s / pre and decodes it on the device
+ * (k_sig_decode, ahead of s^-1); a small batch (the one-launch path) is
+ * decoded by the host parser inside the call.  Results are bit-identical to
+ * bv_verify_batch over the host-decoded arrays either way. */
+typedef struct {
+  bv_batch items;          /* r_be, s_be, pre are ignored and may be NULL  */
+  const uint64_t *sig_off; /* n_items + 1 byte offsets into sig_text       */
+  const uint8_t *sig_text; /* each item's Signature text ("r|s", base 36)  */
+} bv_text_batch;
+
+/* The result contract, the threading and the pinned-memory rule are
+ * bv_verify_batch's; sig_off and sig_text in bv_host_alloc memory are DMA'd
+ * in place too.  BV_E_ARGS (with a bv_last_error text) beyond
+ * bv_verify_batch's cases: sig_off NULL with n_items > 0, sig_off[0] != 0,
+ * sig_off not monotone, sig_text NULL with sig_off[n_items] > 0.  n_items == 0
+ * is BV_OK (the messages are still hashed). */
+int bv_verify_batch_text(bv_ctx *ctx, const bv_text_batch *tb, bv_result *result);
 
 /* Page-locked host memory (hipHostMalloc, portable to every device) for
  * callers that build their batches in place (the cgo shim allocates its
@@ -426,6 +455,13 @@ int bv_get_timing(const bv_ctx *ctx, bv_timing *out);
 /* keys.DecodeSignature + classification: writes 32-byte BE r,s (zero when the
  * class is not OK) and returns the pre byte. */
 uint8_t bv_decode_signature(const char *sig, size_t len, uint8_t r_be[32], uint8_t s_be[32]);
+/* bv_decode_signature over n texts in one call: text i is sig_text[sig_off[i]
+ * .. sig_off[i+1]); writes 32 * n bytes of r and of s (zero where the class is
+ * not OK, as above) and n pre bytes.  BV_OK, or BV_E_ARGS on a NULL pointer
+ * (sig_text may be NULL when every text is empty) or offsets that are not
+ * monotone; n == 0 is BV_OK and reads nothing. */
+int bv_decode_signatures(uint64_t n, const uint64_t *sig_off, const uint8_t *sig_text,
+                         uint8_t *r_be, uint8_t *s_be, uint8_t *pre);
 /* common.DecodeFromString: hex.DecodeString(s[2:]) keeping the prefix decoded
  * before the first error.  Returns the decoded length, or -1 where Go panics
  * (len < 2).  `out` must hold (len-2)/2 bytes. */
