@@ -170,3 +170,208 @@ class BatchBuilder:
         tb, to = _cat(self._text)
         return PackedTextBatch(mb, mo, kb, ko, np.array(self._item_msg, np.uint32),
                                np.array(self._item_key, np.uint32), to, tb)
+
+
+# ----------------------------------------------------------------------------
+# blocks from their fields (bv_block_batch, bv_verify_blocks)
+# ----------------------------------------------------------------------------
+_BLOCK_DTYPES = (("index", np.int64), ("round_received", np.int64), ("timestamp", np.int64),
+                 ("hash_off", np.uint64), ("hash_bytes", np.uint8), ("hash_nil", np.uint8),
+                 ("tx_start", np.uint64), ("tx_off", np.uint64), ("tx_bytes", np.uint8),
+                 ("tx_list_nil", np.uint8), ("tx_nil", np.uint8), ("itx_off", np.uint64), ("itx_json", np.uint8),
+                 ("rcpt_off", np.uint64), ("rcpt_json", np.uint8), ("key_bytes", np.uint8), ("key_off", np.uint64),
+                 ("item_block", np.uint32), ("item_key", np.uint32), ("sig_off", np.uint64), ("sig_text", np.uint8),
+                 ("r_be", np.uint8), ("s_be", np.uint8), ("pre", np.uint8))
+
+
+@dataclass
+class PackedBlockBatch:
+    """BlockBody fields of n blocks and their signatures as items over blocks
+    and validator keys (bv_block_batch): the library builds and hashes every
+    BlockBody.Marshal() itself.  The signatures are text (sig_off / sig_text)
+    or, after decoded(), r_be / s_be / pre."""
+    index: np.ndarray            # i64 [n]
+    round_received: np.ndarray   # i64 [n]
+    timestamp: np.ndarray        # i64 [n]
+    hash_off: np.ndarray         # u64 [3 n + 1]: StateHash, FrameHash, PeersHash of each block
+    hash_bytes: np.ndarray       # u8
+    hash_nil: Optional[np.ndarray]      # u8 [3 n] or None (no nil hash)
+    tx_start: np.ndarray         # u64 [n + 1]
+    tx_off: np.ndarray           # u64 [n_tx + 1]
+    tx_bytes: np.ndarray         # u8
+    tx_list_nil: Optional[np.ndarray]   # u8 [n] or None
+    tx_nil: Optional[np.ndarray]        # u8 [n_tx] or None
+    itx_off: Optional[np.ndarray]       # u64 [n + 1] or None (all nil)
+    itx_json: np.ndarray
+    rcpt_off: Optional[np.ndarray]
+    rcpt_json: np.ndarray
+    key_bytes: np.ndarray        # u8
+    key_off: np.ndarray          # u64 [n_keys + 1]
+    item_block: np.ndarray       # u32 [n_items]
+    item_key: np.ndarray         # u32 [n_items]
+    sig_off: Optional[np.ndarray] = None   # u64 [n_items + 1]
+    sig_text: Optional[np.ndarray] = None  # u8
+    r_be: Optional[np.ndarray] = None      # u8 [n_items, 32]
+    s_be: Optional[np.ndarray] = None
+    pre: Optional[np.ndarray] = None
+
+    @property
+    def n_blocks(self) -> int:
+        return len(self.index)
+
+    @property
+    def n_keys(self) -> int:
+        return len(self.key_off) - 1
+
+    @property
+    def n_items(self) -> int:
+        return len(self.item_block)
+
+    def c_struct(self, keep: list) -> "native.BvBlockBatch":
+        """The bv_block_batch of this batch; the arrays it points at (converted
+        to the C dtypes where needed) are appended to `keep`."""
+        def p(name, dt):
+            a = getattr(self, name)
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        b = native.BvBlockBatch()
+        b.n_blocks, b.n_keys, b.n_items = self.n_blocks, self.n_keys, self.n_items
+        text = self.sig_off is not None
+        for name, dt in _BLOCK_DTYPES:
+            if name in ("r_be", "s_be", "pre") and text:
+                continue
+            setattr(b, name, p(name, dt))
+        if text and not b.sig_text:  # every signature empty: a valid pointer to zero bytes
+            keep.append(np.zeros(1, np.uint8))
+            b.sig_text = keep[-1].ctypes.data
+        return b
+
+    def body_lens(self) -> np.ndarray:
+        """bv_block_body_lens: n + 1 offsets of the serialised bodies."""
+        keep: list = []
+        cb = self.c_struct(keep)
+        off = np.zeros(self.n_blocks + 1, np.uint64)
+        rc = native.lib().bv_block_body_lens(cb, off.ctypes.data)
+        if rc != native.BV_OK:
+            raise native.BvError(rc, "bv_block_body_lens")
+        return off
+
+    def bodies(self):
+        """bv_block_bodies: (msg_bytes u8, msg_off u64 [n + 1]) — every
+        BlockBody.Marshal(), built by the library's host serialiser."""
+        off = self.body_lens()
+        keep: list = []
+        cb = self.c_struct(keep)
+        out = np.zeros(int(off[-1]), np.uint8)
+        rc = native.lib().bv_block_bodies(cb, off.ctypes.data, out.ctypes.data if out.size else None)
+        if rc != native.BV_OK:
+            raise native.BvError(rc, "bv_block_bodies")
+        return out, off
+
+    def decoded(self) -> "PackedBlockBatch":
+        """The same batch with r_be / s_be / pre decoded on the host
+        (bv_decode_signatures) instead of the signature text."""
+        import dataclasses
+
+        if self.sig_off is None:
+            return self
+        pre, r, s = native.decode_signatures(self.sig_off, self.sig_text)
+        return dataclasses.replace(self, sig_off=None, sig_text=None, r_be=r, s_be=s, pre=pre)
+
+    def text_batch(self, bodies=None) -> PackedTextBatch:
+        """The bv_text_batch of the same items over serialised bodies
+        (`bodies` = (msg_bytes, msg_off); default: bodies())."""
+        mb, mo = self.bodies() if bodies is None else bodies
+        return PackedTextBatch(mb, mo, self.key_bytes, self.key_off, self.item_block, self.item_key, self.sig_off,
+                               self.sig_text)
+
+    def staged_bytes(self) -> int:
+        """Bytes bv_verify_blocks stages over PCIe for this batch."""
+        return int(sum(np.asarray(getattr(self, name)).nbytes for name, _ in _BLOCK_DTYPES
+                       if getattr(self, name) is not None))
+
+
+def _fragment(items) -> bytes:
+    """encoding/json of a slice of objects with .json() (or the fragment's
+    bytes as they are); None (nil) -> b"", which the library writes as null."""
+    if items is None:
+        return b""
+    if isinstance(items, (bytes, bytearray)):
+        return bytes(items)
+    return b"[" + b",".join(t.json() for t in items) + b"]"
+
+
+class BlockBatchBuilder:
+    """Incrementally builds a PackedBlockBatch: add_block(body) takes a
+    BlockBody (hashgraph.BlockBody; any object with its fields), add_signature
+    a BlockSignature's block, validator key bytes and Signature text.  Keys
+    are de-duplicated by bytes."""
+
+    def __init__(self):
+        self._blocks = []
+        self._keys: List[bytes] = []
+        self._key_idx: Dict[bytes, int] = {}
+        self._item_block: List[int] = []
+        self._item_key: List[int] = []
+        self._text: List[bytes] = []
+
+    def add_block(self, body) -> int:
+        txs = body.Transactions
+        self._blocks.append((int(body.Index), int(body.RoundReceived), int(body.Timestamp),
+                             [None if h is None else bytes(h) for h in (body.StateHash, body.FrameHash,
+                                                                        body.PeersHash)],
+                             None if txs is None else [None if t is None else bytes(t) for t in txs],
+                             _fragment(body.InternalTransactions), _fragment(body.InternalTransactionReceipts)))
+        return len(self._blocks) - 1
+
+    def add_key(self, pub: bytes) -> int:
+        pub = bytes(pub)
+        k = self._key_idx.get(pub)
+        if k is None:
+            k = self._key_idx[pub] = len(self._keys)
+            self._keys.append(pub)
+        return k
+
+    def add_signature(self, block_index: int, validator_bytes: bytes, signature_text) -> int:
+        if isinstance(signature_text, str):
+            signature_text = signature_text.encode("utf-8")
+        self._item_block.append(int(block_index))
+        self._item_key.append(self.add_key(validator_bytes or b""))
+        self._text.append(bytes(signature_text))
+        return len(self._item_block) - 1
+
+    def pack(self) -> PackedBlockBatch:
+        bl = self._blocks
+        n = len(bl)
+        hashes = [h for b in bl for h in b[3]]
+        hb, ho = _cat([h or b"" for h in hashes])
+        txs = [t for b in bl for t in (b[4] or [])]
+        tx_start = np.zeros(n + 1, np.uint64)
+        if n:
+            tx_start[1:] = np.cumsum([len(b[4] or []) for b in bl], dtype=np.uint64)
+        tb, to = _cat([t or b"" for t in txs])
+
+        def frag(xs):
+            if not any(xs):
+                return None, np.zeros(0, np.uint8)
+            buf, off = _cat(xs)
+            return off, buf
+
+        itx_off, itx_json = frag([b[5] for b in bl])
+        rcpt_off, rcpt_json = frag([b[6] for b in bl])
+        kb, ko = _cat(self._keys)
+        st, so = _cat(self._text)
+        return PackedBlockBatch(
+            index=np.array([b[0] for b in bl], np.int64), round_received=np.array([b[1] for b in bl], np.int64),
+            timestamp=np.array([b[2] for b in bl], np.int64), hash_off=ho, hash_bytes=hb,
+            hash_nil=np.array([h is None for h in hashes], np.uint8) if any(h is None for h in hashes) else None,
+            tx_start=tx_start, tx_off=to, tx_bytes=tb,
+            tx_list_nil=np.array([b[4] is None for b in bl], np.uint8) if any(b[4] is None for b in bl) else None,
+            tx_nil=np.array([t is None for t in txs], np.uint8) if any(t is None for t in txs) else None,
+            itx_off=itx_off, itx_json=itx_json, rcpt_off=rcpt_off, rcpt_json=rcpt_json, key_bytes=kb, key_off=ko,
+            item_block=np.array(self._item_block, np.uint32), item_key=np.array(self._item_key, np.uint32),
+            sig_off=so, sig_text=st)

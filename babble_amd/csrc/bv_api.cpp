@@ -97,12 +97,7 @@ constexpr size_t kChunk = 16ull << 20;         // host-entry staging / PCIe chun
 // host batches whose whole staging layout is at most this cross PCIe as ONE
 // copy: each extra small H2D costs ~20 us of DMA latency on a lone call
 constexpr size_t kSmallStage = 1ull << 20;
-// Host entry: a message longer than this is hashed on the host (hostsha.cpp,
-// the SHA extensions) instead of by one GPU lane — SHA-256 of one message is
-// a serial chain, ~3.2 us a block on a lone lane against ~40 ns on a CPU
-// core: the 54 KB anchor Frame of C5 (853 blocks) took 2.8 ms of device time
-// on its lane (profiles/r04_bench_midround.json c5_fast_sync).
-constexpr uint64_t kHostHashLen = 16 << 10;
+// (kHostHashLen, the longest message a GPU lane hashes: bv_internal.h)
 
 }  // namespace
 
@@ -545,6 +540,7 @@ static int create_impl(bv_ctx *ctx) {
   if (const char *s = getenv("BV_FORCE_K8"))  // (A/B knob: as the BV_F_K8 flag)
     if (atoi(s) != 0) ctx->flags |= BV_F_K8;
   if (const char *s = getenv("BV_LAT_TABLE_KEYS")) ctx->lat_table_keys = (uint32_t)atoi(s);
+  if (const char *s = getenv("BV_BLK_NT")) ctx->blk_nt = atoi(s) == 256 ? 256 : atoi(s) == 64 ? 64 : 0;  // (A/B knob)
   return BV_OK;
 }
 
@@ -584,7 +580,8 @@ extern "C" void bv_destroy(bv_ctx *ctx) {
     if (ctx->has_done) (void)hipEventSynchronize(ctx->ev_done);
   }
   if (ctx->g_table) gtable_release(ctx->device);
-  DevBuf *bufs[] = {&ctx->d_in, &ctx->kc_kxy, &ctx->kc_btabs, &ctx->ev_iota, &ctx->d_stamps, &ctx->d_sig};
+  DevBuf *bufs[] = {&ctx->d_in,     &ctx->kc_kxy, &ctx->kc_btabs,    &ctx->ev_iota,
+                    &ctx->d_stamps, &ctx->d_sig,  &ctx->d_blk_count};
   for (auto *b : bufs) b->release();
   for (auto &sl : ctx->slot) {
     DevBuf *sb[] = {&sl.digests,   &sl.kstatus, &sl.kxy, &sl.bases_jac, &sl.key_sub, &sl.key_pscr,
@@ -1415,7 +1412,7 @@ constexpr uint8_t kSmallPending = 0xFF;      // status sentinel (statuses are 0.
 // cold path that measured 0.32 / 0.40 ms at 256 / 512 items gave a false
 // REJECT on ~1 in 3000 items of a process's first batch and was withdrawn
 // (DESIGN.md section 4, round 5).
-static bool small_batch(bv_ctx *ctx, const bv_batch *b, bool text = false) {
+bool bv_small_batch(bv_ctx *ctx, const bv_batch *b, bool text) {
   if (b->n_items == 0) return false;
   const uint64_t n = std::max<uint64_t>(b->n_items, b->n_msgs);
   if (n > ctx->small_max) {
@@ -1436,7 +1433,7 @@ static bool small_batch(bv_ctx *ctx, const bv_batch *b, bool text = false) {
 // The host parser (bv_decode_signature) writes r, s and pre straight into
 // the mapped buffer, so k_small and the host item records see what they see
 // for a bv_verify_batch call over the decoded arrays.
-static int small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res, const bv_sig_text *sig = nullptr) {
+int bv_small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res, const bv_sig_text *sig) {
   const auto t0 = std::chrono::steady_clock::now();
   const uint64_t n_msgs = b->n_msgs, n_items = b->n_items;
   const uint32_t n_keys = b->n_keys;
@@ -1615,10 +1612,10 @@ extern "C" int bv_verify_batch(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
   if (!ctx || !b || !res) return BV_E_ARGS;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
-  if (ctx->small_path && small_batch(ctx, b)) {
+  if (ctx->small_path && bv_small_batch(ctx, b)) {
     int rc = bv_validate_host_batch(ctx, b);
     if (rc != BV_OK) return rc;
-    rc = small_verify(ctx, b, res);
+    rc = bv_small_verify(ctx, b, res);
     return rc == BV_OK ? rc : bv_drain(ctx, ctx->stream, rc);
   }
   bv_host_call call;
@@ -1629,7 +1626,7 @@ extern "C" int bv_verify_batch(bv_ctx *ctx, const bv_batch *b, bv_result *res) {
 
 // The signature text of an item batch (bv_verify_batch_text): offsets from 0,
 // monotone (checked on the pool), bytes present when any text is non-empty.
-static int validate_sig_text(bv_ctx *ctx, uint64_t n_items, const bv_sig_text &sig) {
+int bv_validate_sig_text(bv_ctx *ctx, uint64_t n_items, const bv_sig_text &sig) {
   if (!sig.off) return bv_fail(ctx, BV_E_ARGS, "null sig_off");
   if (sig.off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "sig_off[0] != 0");
   const uint64_t *off = sig.off;
@@ -1651,12 +1648,12 @@ extern "C" int bv_verify_batch_text(bv_ctx *ctx, const bv_text_batch *tb, bv_res
   b.r_be = b.s_be = b.pre = nullptr;
   // (no items: no text either; the messages are hashed as by bv_verify_batch)
   const bv_sig_text text{tb->sig_off, tb->sig_text}, *sig = b.n_items ? &text : nullptr;
-  int rc = sig ? validate_sig_text(ctx, b.n_items, text) : BV_OK;
+  int rc = sig ? bv_validate_sig_text(ctx, b.n_items, text) : BV_OK;
   if (rc != BV_OK) return rc;
-  if (ctx->small_path && small_batch(ctx, &b, sig != nullptr)) {
+  if (ctx->small_path && bv_small_batch(ctx, &b, sig != nullptr)) {
     rc = bv_validate_host_batch(ctx, &b, sig != nullptr);
     if (rc != BV_OK) return rc;
-    rc = small_verify(ctx, &b, res, sig);
+    rc = bv_small_verify(ctx, &b, res, sig);
     return rc == BV_OK ? rc : bv_drain(ctx, ctx->stream, rc);
   }
   bv_host_call call;

@@ -38,6 +38,13 @@ hipError_t ev_body_hash(hipStream_t st, const bv_event_batch &b, uint64_t e0, ui
 // the same over a shard's slices (evjson.h EvjBases): [e0, e1) are the whole batch's event indices
 hipError_t ev_body_hash_rb(hipStream_t st, const bv_event_batch &b, uint64_t e0, uint64_t e1, const EvjBases &bs,
                            uint32_t *dig);
+// BlockBody JSON of blocks [b0, b1) built and hashed, one lane per block (blkjson.h); the blocks in long_idx
+// (sorted, n_long of them; device array) are skipped.  nt: lanes per workgroup, 64 or 256 (0: the default)
+hipError_t blk_body_hash(hipStream_t st, const bv_block_batch &b, uint64_t b0, uint64_t b1, const uint64_t *long_idx,
+                         uint64_t n_long, uint32_t *dig, int nt = 0);
+// count[item_block[i]] += 1 for every item whose status is BV_ACCEPT (count zeroed by the caller)
+hipError_t blk_tally(hipStream_t st, uint64_t n_items, const uint32_t *item_block, const uint8_t *status,
+                     uint32_t *count);
 hipError_t iota(hipStream_t, uint64_t, uint32_t *);
 hipError_t sig_decode(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be, uint8_t *s_be,
                       uint8_t *pre);
@@ -218,6 +225,14 @@ struct CopyPool {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Host entries: a message (bv_verify_batch) or block body (bv_verify_blocks)
+// longer than this is hashed on the host (hostsha.cpp, the SHA extensions)
+// instead of by one GPU lane — SHA-256 of one message is a serial chain,
+// ~3.2 us a block on a lone lane against ~40 ns on a CPU core: the 54 KB
+// anchor Frame of C5 (853 blocks) took 2.8 ms of device time on its lane
+// (profiles/r04_bench_midround.json c5_fast_sync).
+constexpr uint64_t kHostHashLen = 16 << 10;
+
 // timing / ordering events (see bv_read_timing)
 enum {
   E_START, E_FORK, E_SHA, E_SCALAR, E_G, E_JOINED, E_END, E_KEYS, E_SINV,
@@ -324,6 +339,11 @@ struct bv_ctx {
   DevBuf kc_kxy, kc_btabs;
   // bv_verify_events: body lengths, parent-hex positions, offsets, bodies
   DevBuf ev_iota;
+  // bv_verify_blocks: valid_count on the device; the bodies a small batch builds on the host and their offsets
+  DevBuf d_blk_count;
+  std::vector<uint8_t> blk_bodies;
+  std::vector<uint64_t> blk_off;
+  int blk_nt = 0;  // BV_BLK_NT (A/B knob): lanes per workgroup of k_blk_body_hash, 64 or 256 (0: the default)
   HostDagScratch dag_scratch;  // in-batch DAG batches: bodies built and hashed on the host (hostdag.cpp)
   // A/B knobs, read once at bv_create (never per call): host-entry message
   // chunk (BV_HOST_CHUNK_MB, >= 1 MB), event staging chunk (BV_EV_CHUNK_MB,
@@ -469,6 +489,14 @@ void bv_kc_release(bv_ctx *ctx);  // free every cached table (bv_destroy, after 
 int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_result *res = nullptr,
                    const bv_sig_text *sig = nullptr);
 int bv_host_finish(bv_ctx *ctx, const bv_batch *b, bv_result *res, bv_host_call *call, bool bits_out);
+// The one-launch small path of the host entries (bv_api.cpp): bv_small_batch
+// is the routing rule (item and message counts, message lengths, the key
+// cache's state), bv_small_verify the call itself over a validated batch.
+// `sig` (may be null; validated by the caller): the items' signature text.
+bool bv_small_batch(bv_ctx *ctx, const bv_batch *b, bool text = false);
+int bv_small_verify(bv_ctx *ctx, const bv_batch *b, bv_result *res, const bv_sig_text *sig = nullptr);
+// bv_verify_batch_text's checks of sig_off / sig_text (and their bv_last_error texts)
+int bv_validate_sig_text(bv_ctx *ctx, uint64_t n_items, const bv_sig_text &sig);
 // bv_verify_events' bulk path over one event range of a batch (bv_events.cpp):
 // events [a, z) and the parent hashes [hash_lo, hash_hi) its BV_PARENT_HASH
 // parents name (bv_plan_event_shards).  bv_validate_events checks the WHOLE

@@ -16,6 +16,7 @@ outcomes by the batch functions (a batch cannot panic half way).
 Batch entry points (what the cgo shim in INTEGRATION.md exposes to Go):
   verify_events(events)            -> [Outcome]   (Event.Verify for each)
   verify_block_signatures(b, sigs) -> [Outcome]   (Block.Verify for each)
+  check_blocks(blocks, peer_sets)  -> [error or None]  (CheckBlock for each, one call)
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import gojson as J
-from .batch import BatchBuilder
+from .batch import BatchBuilder, BlockBatchBuilder
 from .native import ACCEPT, REF_PANIC, REJECT, REJECT_ERR, ReferencePanic, hex_decode
 
 _default = None
@@ -365,12 +366,20 @@ def compose_event_outcome(itx_statuses: Sequence[Optional[int]], event_status: i
 
 
 def verify_block_signatures(block: Block, sigs: Sequence[BlockSignature], verifier=None,
-                            text: bool = False) -> List[Outcome]:
+                            text: bool = False, fields: bool = False) -> List[Outcome]:
     """Block.Verify for every signature: the body is hashed once, not per
     signature (block.go:344 re-hashes on every call).  text=True: the
-    signature texts go to the library undecoded (bv_verify_batch_text)."""
+    signature texts go to the library undecoded (bv_verify_batch_text).
+    fields=True: so does the BlockBody, as its fields — the library builds
+    and hashes BlockBody.Marshal() itself (bv_verify_blocks)."""
     if not sigs:
         return []
+    if fields:
+        kb = BlockBatchBuilder()
+        m = kb.add_block(block.Body)
+        items = [kb.add_signature(m, s.Validator or b"", s.Signature) for s in sigs]
+        res = (verifier or default_verifier()).verify_blocks(kb.pack(), counts=False)
+        return [_item_outcome(int(res.status[k]), s.Signature) for s, k in zip(sigs, items)]
     bb = BatchBuilder()
     m = bb.add_msg(block.Body.Marshal())
     items = [bb.add_item(m, bb.add_key(s.Validator or b""), s.Signature) for s in sigs]
@@ -396,13 +405,49 @@ def check_block(block: Block, peer_set: PeerSet, verifier=None) -> Optional[str]
     return None
 
 
+def check_blocks(blocks: Sequence[Block], peer_sets: Sequence[PeerSet], verifier=None) -> List[object]:
+    """Hashgraph.CheckBlock for every (block, peer set) pair in ONE
+    bv_verify_blocks call: per block exactly what check_block returns (None
+    or the error text).  Where check_block raises ReferencePanic, that
+    block's entry is a ReferencePanic instance (a batch cannot panic half
+    way).  The bodies go to the library as fields; the count of valid
+    signatures per block is the library's valid_count (tallied on the
+    device for bulk batches); only signatures of validators in the block's
+    peer set are listed, as CheckBlock skips the others before Block.Verify."""
+    out: List[object] = [None] * len(blocks)
+    kb = BlockBatchBuilder()
+    slot = []  # (position in `blocks`, block index in the batch, its items)
+    for i, (block, ps) in enumerate(zip(blocks, peer_sets)):
+        bph = block.PeersHash()
+        if bph is None or ps.Hash(verifier) != bph:  # (as check_block: a nil PeersHash never matches)
+            out[i] = "Wrong PeerSet"
+            continue
+        m = kb.add_block(block.Body)
+        items = [kb.add_signature(m, s.Validator or b"", s.Signature)
+                 for s in block.GetSignatures() if s.ValidatorHex() in ps.ByPubKey]
+        slot.append((i, m, items))
+    if not slot:
+        return out
+    res = (verifier or default_verifier()).verify_blocks(kb.pack(), counts=True)
+    for i, m, items in slot:
+        if any(int(res.status[k]) == REF_PANIC for k in items):
+            out[i] = ReferencePanic("Block.Verify panics")
+            continue
+        valid, need = int(res.valid_count[m]), peer_sets[i].TrustCount()
+        if valid <= need:
+            out[i] = "Not enough valid signatures: got %d, need %d" % (valid, need)
+    return out
+
+
 def process_sig_pool(pending: Sequence[BlockSignature], get_block: Callable[[int], Optional[Block]],
-                     get_peer_set: Callable[[int], Optional[PeerSet]], verifier=None, text: bool = False):
+                     get_peer_set: Callable[[int], Optional[PeerSet]], verifier=None, text: bool = False,
+                     fields: bool = False):
     """Hashgraph.ProcessSigPool (hashgraph.go:1295-1367) over `pending` in the
     given (map) order.  Returns (appended signatures, error or None); a
     DecodeSignature error aborts the pool at that signature, as in Go.
     All candidate signatures are verified in one device batch first
-    (text=True: from their texts, bv_verify_batch_text)."""
+    (text=True: from their texts, bv_verify_batch_text; fields=True: the
+    blocks as their fields too, bv_verify_blocks)."""
     cands = []
     for bs in pending:
         blk = get_block(bs.Index)
@@ -412,14 +457,22 @@ def process_sig_pool(pending: Sequence[BlockSignature], get_block: Callable[[int
         if ps is None or bs.ValidatorHex() not in ps.ByPubKey:
             continue
         cands.append((bs, blk))
-    bb = BatchBuilder()
+    bb = BlockBatchBuilder() if fields else BatchBuilder()
     msg_of = {}
     items = []
     for bs, blk in cands:
         if id(blk) not in msg_of:
-            msg_of[id(blk)] = bb.add_msg(blk.Body.Marshal())
-        items.append(bb.add_item(msg_of[id(blk)], bb.add_key(bs.Validator or b""), bs.Signature))
-    res = _verify_items(bb, verifier, text) if items else None
+            msg_of[id(blk)] = bb.add_block(blk.Body) if fields else bb.add_msg(blk.Body.Marshal())
+        if fields:
+            items.append(bb.add_signature(msg_of[id(blk)], bs.Validator or b"", bs.Signature))
+        else:
+            items.append(bb.add_item(msg_of[id(blk)], bb.add_key(bs.Validator or b""), bs.Signature))
+    if not items:
+        res = None
+    elif fields:
+        res = (verifier or default_verifier()).verify_blocks(bb.pack(), counts=False)
+    else:
+        res = _verify_items(bb, verifier, text)
     appended = []
     for (bs, blk), k in zip(cands, items):
         o = _item_outcome(int(res.status[k]), bs.Signature)

@@ -39,6 +39,7 @@ EXPORTS = (
     "bv_kc_register", "bv_arena_create", "bv_arena_destroy", "bv_arena_reserve",
     "bv_group_verify_events", "bv_group_kc_register", "bv_plan_event_shards",
     "bv_kc_small_tables", "bv_verify_batch_text", "bv_decode_signatures",
+    "bv_verify_blocks", "bv_block_body_lens", "bv_block_bodies",
 )
 
 
@@ -64,6 +65,20 @@ class BvTextBatch(ctypes.Structure):
         ("items", BvBatch),
         ("sig_off", ctypes.c_void_p),
         ("sig_text", ctypes.c_void_p),
+    ]
+
+
+class BvBlockBatch(ctypes.Structure):
+    """bv_block_batch: BlockBody fields and the block signatures as items."""
+    _P = ctypes.c_void_p
+    _fields_ = [
+        ("n_blocks", ctypes.c_uint64), ("index", _P), ("round_received", _P), ("timestamp", _P),
+        ("hash_off", _P), ("hash_bytes", _P), ("hash_nil", _P),
+        ("tx_start", _P), ("tx_off", _P), ("tx_bytes", _P), ("tx_list_nil", _P), ("tx_nil", _P),
+        ("itx_off", _P), ("itx_json", _P), ("rcpt_off", _P), ("rcpt_json", _P),
+        ("n_keys", ctypes.c_uint32), ("key_bytes", _P), ("key_off", _P),
+        ("n_items", ctypes.c_uint64), ("item_block", _P), ("item_key", _P),
+        ("sig_off", _P), ("sig_text", _P), ("r_be", _P), ("s_be", _P), ("pre", _P),
     ]
 
 
@@ -134,6 +149,12 @@ def lib() -> ctypes.CDLL:
     L.bv_verify_batch_text.restype = ctypes.c_int
     L.bv_decode_signatures.argtypes = [ctypes.c_uint64, P, P, P, P, P]
     L.bv_decode_signatures.restype = ctypes.c_int
+    L.bv_verify_blocks.argtypes = [P, ctypes.POINTER(BvBlockBatch), ctypes.POINTER(BvResult), P]
+    L.bv_verify_blocks.restype = ctypes.c_int
+    L.bv_block_body_lens.argtypes = [ctypes.POINTER(BvBlockBatch), P]
+    L.bv_block_body_lens.restype = ctypes.c_int
+    L.bv_block_bodies.argtypes = [ctypes.POINTER(BvBlockBatch), P, P]
+    L.bv_block_bodies.restype = ctypes.c_int
     L.bv_verify_batch_device.argtypes = [P, ctypes.POINTER(BvBatch), ctypes.POINTER(BvResult), P, ctypes.c_int]
     L.bv_verify_batch_device.restype = ctypes.c_int
     L.bv_sha256_batch.argtypes = [P, ctypes.c_uint64, P, P, P]

@@ -27,6 +27,14 @@ class VerifyResult:
     accept_bits: np.ndarray  # [ceil(n_items/64)] u64
 
 
+@dataclass
+class BlockVerifyResult(VerifyResult):
+    """verify_blocks: msg_hash holds every BlockBody.Hash; valid_count[b] is
+    the number of block b's items with status ACCEPT (CheckBlock's tally;
+    None when not asked for)."""
+    valid_count: Optional[np.ndarray] = None  # [n_blocks] u32
+
+
 def _p(a: np.ndarray) -> int:
     return a.ctypes.data if a is not None and a.size else 0
 
@@ -188,6 +196,31 @@ class Verifier:
         ctb = _ctbatch(tb, keep)
         r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
         self._check(self._L.bv_verify_batch_text(self._ctx, ctypes.byref(ctb), ctypes.byref(r)))
+        return res
+
+    def verify_blocks(self, pb, counts: bool = True, status: bool = True) -> "BlockVerifyResult":
+        """bv_verify_blocks over a batch.PackedBlockBatch: the library builds
+        and hashes every BlockBody.Marshal() (on the device for bulk batches)
+        and verifies the block signatures.  counts: also CheckBlock's tally
+        per block (valid_count).  status=False: no per-item status array is
+        copied back (res.status is None)."""
+        nb, ni, nw = max(pb.n_blocks, 1), max(pb.n_items, 1), max((pb.n_items + 63) // 64, 1)
+        res = BlockVerifyResult(np.empty((nb, 32), np.uint8), np.empty(ni, np.uint8) if status else None,
+                                np.empty(nw, np.uint64), np.empty(nb, np.uint32) if counts else None)
+        self.verify_blocks_into(pb, res)
+        return BlockVerifyResult(res.msg_hash[: pb.n_blocks], res.status[: pb.n_items] if status else None,
+                                 res.accept_bits[: (pb.n_items + 63) // 64],
+                                 res.valid_count[: pb.n_blocks] if counts else None)
+
+    def verify_blocks_into(self, pb, res: "BlockVerifyResult") -> "BlockVerifyResult":
+        """bv_verify_blocks into caller-owned result arrays, any of them None
+        (PinnedArena arrays are reached by DMA; so are the fields of a batch
+        built by PinnedArena.block_batch)."""
+        keep: list = []
+        cb = pb.c_struct(keep)
+        r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
+        vc = getattr(res, "valid_count", None)
+        self._check(self._L.bv_verify_blocks(self._ctx, ctypes.byref(cb), ctypes.byref(r), _p(vc) or None))
         return res
 
     def sync(self) -> None:
@@ -526,6 +559,20 @@ class PinnedArena:
                                self.copy(tb.key_bytes), self.copy(tb.key_off.astype(np.uint64)),
                                self.copy(tb.item_msg.astype(np.uint32)), self.copy(tb.item_key.astype(np.uint32)),
                                self.copy(tb.sig_off.astype(np.uint64)), self.copy(tb.sig_text))
+
+    def block_batch(self, pb):
+        """The same batch.PackedBlockBatch with every array in pinned memory
+        (in the dtypes the C struct takes, so none is converted again)."""
+        import dataclasses
+
+        from .batch import _BLOCK_DTYPES
+
+        dt = dict(_BLOCK_DTYPES)
+        out = {}
+        for f in dataclasses.fields(pb):
+            a = getattr(pb, f.name)
+            out[f.name] = None if a is None else self.copy(np.asarray(a).astype(dt[f.name], copy=False))
+        return type(pb)(**out)
 
     def wire(self, eb):
         """The same events.EventWireBatch with every array in pinned memory

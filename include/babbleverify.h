@@ -15,6 +15,9 @@
  *   bv_verify_batch_text  the same items from their Signature text:
  *                     keys.DecodeSignature applied by the library
  *                                                             src/crypto/keys/signature.go:31-39
+ *   bv_verify_blocks  the same for block signatures, from the
+ *                     BlockBody's fields: BlockBody.Marshal   src/hashgraph/block.go:16-36
+ *                     and CheckBlock's tally                  src/hashgraph/hashgraph.go:1599-1630
  *   bv_sha256_batch   N x crypto.SHA256                       src/crypto/hash.go:8-13
  *   bv_decode_signature  keys.DecodeSignature + the sign/range
  *                     pre-checks of ecdsa.Verify              src/crypto/keys/signature.go:31-39
@@ -436,6 +439,76 @@ int bv_group_kc_register(bv_group *g, uint32_t n_keys, const uint8_t *key_bytes,
  * n_parent_hashes are read. */
 int bv_plan_event_shards(const bv_event_batch *events, int n_shards, uint64_t *event_bounds, uint64_t *hash_lo,
                          uint64_t *hash_hi);
+
+/* Blocks from their fields: Block.Verify (src/hashgraph/block.go:343-357),
+ * CheckBlock (hashgraph.go:1599-1630), ProcessSigPool and the fast-forward
+ * check without the caller serialising anything.  Instead of
+ * BlockBody.Marshal() per block the caller passes the BlockBody's fields
+ * (block.go:16-26); the device builds every canonical body (Go 1.13
+ * encoding/json of the exported fields in declaration order, then '\n',
+ * bit-exact), hashes it as it is built (no body is stored) and verifies the
+ * block signatures listed as items over blocks and validator keys, as
+ * bv_batch items are over messages.  Bodies longer than 16 KiB are built and
+ * hashed by the library's host threads beside the device's hashing; a batch
+ * that bv_verify_batch_text would run on its one-launch small path (same item
+ * count and keys) has its bodies built on the host and takes that path. */
+typedef struct {
+  uint64_t n_blocks;
+  const int64_t *index, *round_received, *timestamp; /* per block (Go int / int64)      */
+  /* StateHash, FrameHash, PeersHash: 3 byte strings per block, in that order */
+  const uint64_t *hash_off;   /* 3 * n_blocks + 1 offsets into hash_bytes (any length)  */
+  const uint8_t *hash_bytes;
+  const uint8_t *hash_nil;    /* 3 per block, 1: that []byte is nil -> null (NULL: none) */
+  /* Transactions, exactly as in bv_event_batch */
+  const uint64_t *tx_start;   /* n_blocks + 1 */
+  const uint64_t *tx_off; const uint8_t *tx_bytes;
+  const uint8_t *tx_list_nil; /* per block */
+  const uint8_t *tx_nil;      /* per tx    */
+  /* verbatim encoding/json of the slices; an empty fragment = nil -> null ("[]" is a fragment);
+   * a NULL offset array: every block's slice is nil */
+  const uint64_t *itx_off;  const uint8_t *itx_json;   /* InternalTransactions        */
+  const uint64_t *rcpt_off; const uint8_t *rcpt_json;  /* InternalTransactionReceipts */
+  /* the signatures: items over blocks and validator keys, as bv_batch items over messages */
+  uint32_t n_keys; const uint8_t *key_bytes; const uint64_t *key_off;
+  uint64_t n_items;
+  const uint32_t *item_block, *item_key;
+  const uint64_t *sig_off; const uint8_t *sig_text;    /* BlockSignature.Signature text, OR */
+  const uint8_t *r_be, *s_be, *pre;                    /* host-decoded, as bv_event_batch   */
+} bv_block_batch;
+
+/* The result contract is bv_verify_batch_text's: msg_hash is 32 * n_blocks
+ * bytes and holds every BlockBody.Hash (a block without items is still
+ * hashed); status and accept_bits are per item, in the caller's item order,
+ * and the items may come in any block order; the pinned-memory rule (every
+ * array and result buffer in bv_host_alloc memory moves by DMA in place), the
+ * threading and the bv_last_error texts are the same.  When sig_text is
+ * non-NULL r_be / s_be / pre are ignored.
+ * valid_count (n_blocks words, may be NULL): valid_count[b] = the number of
+ * items of block b whose status is BV_ACCEPT, tallied on the device (on the
+ * host for a batch that takes the one-launch small path, whose statuses are
+ * written into host memory) — CheckBlock's count.  A caller that passes
+ * status == NULL gets 4 * n_blocks bytes back instead of a per-item array.
+ * The caller lists ONLY the signatures of validators in the block's peer
+ * set: CheckBlock skips the others before Block.Verify (Go `continue`s,
+ * hashgraph.go:1612-1616), so they must not be counted.  BV_REF_PANIC items
+ * count as not accepted and stay visible in status.
+ * BV_E_ARGS (with a bv_last_error text): a NULL required array, offsets that
+ * are not monotone or do not start at 0, item_block >= n_blocks, item_key >=
+ * n_keys, more than 2^32 blocks, neither sig_text nor r_be / s_be, and
+ * everything bv_verify_batch_text rejects for sig_off / sig_text.  n_blocks
+ * == 0 and n_items == 0 are BV_OK. */
+int bv_verify_blocks(bv_ctx *ctx, const bv_block_batch *blocks, bv_result *result,
+                     uint32_t *valid_count /* n_blocks, may be NULL */);
+/* Host helpers (no device): the serialiser bv_verify_blocks runs, as
+ * bv_decode_signatures is the parser's public form.  bv_block_body_lens
+ * writes n_blocks + 1 offsets (body_off[0] = 0, body b is body_off[b+1] -
+ * body_off[b] bytes long); bv_block_bodies writes body b at out +
+ * body_off[b] for any monotone body_off that leaves each body its length.
+ * Only the block fields are read (not the keys or items).  BV_E_ARGS on a
+ * NULL pointer, on block offsets that are not monotone or do not start at 0
+ * and on a body_off slot shorter than its body; n_blocks == 0 is BV_OK. */
+int bv_block_body_lens(const bv_block_batch *blocks, uint64_t *body_off /* n_blocks + 1 */);
+int bv_block_bodies(const bv_block_batch *blocks, const uint64_t *body_off, uint8_t *out);
 
 /* SHA-256 of n messages (host buffers) -> 32*n bytes. */
 int bv_sha256_batch(bv_ctx *ctx, uint64_t n_msgs, const uint8_t *msg_bytes,
