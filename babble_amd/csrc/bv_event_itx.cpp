@@ -1,0 +1,608 @@
+// bv_verify_events_itx: the whole of Event.Verify in one call
+// (include/babbleverify.h; itxjson.h).  The events as bv_verify_events takes
+// them, and their InternalTransactions from fields: each
+// InternalTransactionBody.Marshal() is built and hashed on the device
+// (k_itx_body_hash), each EventBody with its InternalTransactions member too
+// (k_ev_body_hash_itx; a batch with in-batch parents on the host in
+// topological order, hostdag.cpp, as bv_verify_events does), then the verify
+// pipeline runs over n_events + n_itx items (item e: event e under its
+// creator's key; item n_events + i: ITX i under the key its PubKeyHex decodes
+// to) and k_ev_compose folds the statuses per event.
+//
+// Host work is validation, the hex decode of every PubKeyHex into the combined
+// key array (the creators' keys, then every distinct ITX key that is none of
+// them; the key cache and the key path are chosen from host bytes) and
+// the staging, in the order the device can use it: the keys, the signature
+// text (the events' followed by the ITXs' Signature strings: k_sig_decode,
+// s^-1), then the fields.  A batch without ITXs is bv_verify_events over the
+// same events with nil / "[]" fragments.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "bv_internal.h"
+#include "hostsha.h"
+#include "itxjson.h"
+
+#define HIPCHK(expr, code, what)                               \
+  do {                                                         \
+    hipError_t _e = (expr);                                    \
+    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
+  } while (0)
+
+namespace {
+
+constexpr uint64_t kGrain = 1 << 15;
+constexpr uint64_t kItxKeyMax = 66;  // a decoded key is stored as its first 66 bytes (any length but 0 / 65 is malformed)
+
+bool par(CopyPool *pool, uint64_t n, uint64_t grain, const std::function<bool(uint64_t, uint64_t)> &fn) {
+  return pool ? pool->parallel_for(n, grain, fn) : fn(0, n);
+}
+
+bool monotone(CopyPool *pool, const uint64_t *off, uint64_t n) {
+  return par(pool, n, kGrain, [off](uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++)
+      if (off[i] > off[i + 1]) return false;
+    return true;
+  });
+}
+
+// The ITX fields (what itxjson.h reads): nullptr, or what is wrong.
+const char *check_itx(const bv_event_itx_batch *x, CopyPool *pool) {
+  const uint64_t n = x->events.n_events;
+  if (x->events.itx_off || x->events.itx_json) return "events.itx_off / itx_json must be NULL (the ITXs come from fields)";
+  if (!x->itx_start) return "null itx_start";
+  if (x->itx_start[0] != 0) return "itx_start[0] != 0";
+  if (!monotone(pool, x->itx_start, n)) return "itx_start not monotone";
+  const uint64_t m = x->itx_start[n];
+  if (n > (1ull << 32) || m > (1ull << 32) || n + m > (1ull << 32)) return "more than 2^32 events and ITXs";
+  if (!m) return nullptr;
+  if (!x->itx_type) return "null itx_type";
+  if (!x->itx_str_off) return "null itx_str_off";
+  if (x->itx_str_off[0] != 0) return "itx_str_off[0] != 0";
+  if (!monotone(pool, x->itx_str_off, 4 * m)) return "itx_str_off not monotone";
+  if (x->itx_str_off[4 * m] && !x->itx_str) return "null itx_str";
+  return nullptr;
+}
+
+// The event fields the serialiser reads, without a context (the host
+// helpers): bv_verify_events' rules.
+const char *check_event_fields(const bv_event_batch *b) {
+  const uint64_t n = b->n_events;
+  if (!n) return nullptr;
+  if (!b->creator || !b->index || !b->timestamp || !b->parent_kind || !b->parent_ref || !b->tx_start || !b->key_off)
+    return "null event array";
+  if (b->key_off[0] != 0) return "key_off[0] != 0";
+  for (uint32_t k = 0; k < b->n_keys; k++)
+    if (b->key_off[k] > b->key_off[k + 1]) return "key_off not monotone";
+  if (b->key_off[b->n_keys] && !b->key_bytes) return "null key bytes";
+  if (b->tx_start[0] != 0) return "tx_start[0] != 0";
+  if (!monotone(nullptr, b->tx_start, n)) return "tx_start not monotone";
+  const uint64_t n_tx = b->tx_start[n];
+  if (n_tx && (!b->tx_off || b->tx_off[0] != 0 || !monotone(nullptr, b->tx_off, n_tx))) return "bad tx_off";
+  if (n_tx && b->tx_off[n_tx] && !b->tx_bytes) return "null tx bytes";
+  if (b->bsig_off && (b->bsig_off[0] != 0 || !monotone(nullptr, b->bsig_off, n))) return "bad bsig_off";
+  if (b->bsig_off && b->bsig_off[n] && !b->bsig_json) return "null fragment bytes";
+  for (uint64_t e = 0; e < n; e++) {
+    if (b->creator[e] >= b->n_keys) return "creator out of range";
+    for (int p = 0; p < 2; p++) {
+      const uint8_t k = b->parent_kind[2 * e + p];
+      const uint64_t r = b->parent_ref[2 * e + p];
+      if (k > BV_PARENT_EVENT) return "bad parent kind";
+      if (k == BV_PARENT_HASH && (r >= b->n_parent_hashes || !b->parent_hashes)) return "parent hash out of range";
+      if (k == BV_PARENT_EVENT && r >= e) return "an in-batch parent must precede its child";
+    }
+  }
+  return nullptr;
+}
+
+// common.DecodeFromString of ITX i's PubKeyHex into at most kItxKeyMax bytes:
+// the decoded length (capped), or -1 when the string is shorter than 2 bytes
+// (the reference panics)
+int64_t decode_key(const bv_event_itx_batch *x, uint64_t i, uint8_t *out, std::vector<uint8_t> &big) {
+  const uint64_t len = itx_str_len(*x, i, ITX_PUBKEYHEX);
+  if (len < 2) return -1;
+  const char *s = (const char *)itx_str_ptr(*x, i, ITX_PUBKEYHEX);
+  if ((len - 2) / 2 <= kItxKeyMax) return bv_hex_decode(s, len, out);
+  big.resize((len - 2) / 2);
+  const int64_t k = std::min<int64_t>(bv_hex_decode(s, len, big.data()), (int64_t)kItxKeyMax);
+  memcpy(out, big.data(), (size_t)k);
+  return k;
+}
+
+// Event.Verify's fold on the host (the small path; k_ev_compose otherwise)
+void compose_host(const bv_event_itx_batch *x, const uint8_t *item_status, const uint8_t *force, bv_result *res,
+                  bv_event_itx_out *out) {
+  const uint64_t n = x->events.n_events;
+  if (res->accept_bits) memset(res->accept_bits, 0, (n + 63) / 64 * 8);
+  for (uint64_t e = 0; e < n; e++) {
+    uint8_t st = item_status[e];
+    uint32_t by = BV_EV_SELF;
+    const uint64_t i0 = x->itx_start[e], i1 = x->itx_start[e + 1];
+    for (uint64_t i = i0; i < i1; i++) {
+      const uint8_t c = force[i] ? (uint8_t)BV_REF_PANIC : item_status[n + i];
+      if (out && out->itx_status) out->itx_status[i] = c;
+      if (by == BV_EV_SELF && c != BV_ACCEPT) {
+        by = (uint32_t)(i - i0);
+        st = c == BV_REJECT ? (uint8_t)BV_EV_ITX_INVALID : c;
+      }
+    }
+    if (res->status) res->status[e] = st;
+    if (out && out->decided_by) out->decided_by[e] = by;
+    if (res->accept_bits && st == BV_ACCEPT) res->accept_bits[e >> 6] |= 1ull << (e & 63);
+  }
+}
+
+// A batch the text entry would run on its one-launch small path (the same
+// routing rule over the same item count and keys): every body, the events' and
+// the ITXs', is built here (a batch with in-batch parents through hostdag.cpp,
+// which leaves the bodies with their parents' hex spliced in), that path hashes
+// them on the host (hostsha) and verifies the items in one launch, and the
+// fold is done on the host.  *taken = false: the bulk pipeline's.
+int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out, bool dag,
+                const std::vector<uint32_t> &order, const std::vector<uint32_t> &level_off,
+                const std::vector<uint64_t> &koff, const std::vector<uint8_t> &kfix,
+                const std::vector<uint32_t> &ikey, const std::vector<uint32_t> &usrc,
+                const std::vector<uint8_t> &force, const std::vector<uint64_t> &soff, bool *taken) {
+  const bv_event_batch *eb = &x->events;
+  const uint64_t n = eb->n_events, m = x->itx_start[n], N = n + m;
+  const uint32_t n_keys = eb->n_keys;
+  const uint64_t K = (uint64_t)n_keys + usrc.size();
+  *taken = false;
+  std::vector<uint64_t> moff(N + 1, 0);
+  std::vector<uint8_t> bodies;
+  uint32_t pp[2];
+  if (dag) {
+    std::vector<uint8_t> evdig(n * 32);
+    const HostParFor pf = [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
+      ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
+        fn(lo, hi);
+        return true;
+      });
+    };
+    bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, ctx->dag_scratch,
+                         evdig.data());
+    memcpy(moff.data(), ctx->dag_scratch.off.data(), (n + 1) * 8);
+  } else {
+    for (uint64_t e = 0; e < n; e++) moff[e + 1] = moff[e] + evj_len(*x, e, pp);
+  }
+  for (uint64_t i = 0; i < m; i++) moff[n + i + 1] = moff[n + i] + itx_body_len(*x, i);
+  bodies.resize(moff[N] + 64);
+  if (dag) {
+    memcpy(bodies.data(), ctx->dag_scratch.bodies.data(), moff[n]);
+  } else {
+    for (uint64_t e = 0; e < n; e++) evj_write(*x, e, bodies.data() + moff[e]);
+  }
+  for (uint64_t i = 0; i < m; i++) {
+    EvjMem o{bodies.data() + moff[n + i]};
+    itx_body_emit(*x, i, o);
+  }
+  std::vector<uint8_t> kb(koff[K] + 64), text(soff[N] + 1);
+  if (koff[n_keys]) memcpy(kb.data(), eb->key_bytes, koff[n_keys]);
+  if (soff[n]) memcpy(text.data(), eb->sig_text, soff[n]);
+  std::vector<uint32_t> item_msg(N), item_key(N);
+  for (uint64_t e = 0; e < n; e++) item_msg[e] = (uint32_t)e, item_key[e] = eb->creator[e];
+  for (size_t u = 0; u < usrc.size(); u++) {
+    const uint64_t kl = koff[n_keys + u + 1] - koff[n_keys + u];
+    if (kl) memcpy(kb.data() + koff[n_keys + u], kfix.data() + (size_t)usrc[u] * kItxKeyMax, kl);
+  }
+  for (uint64_t i = 0; i < m; i++) {
+    item_msg[n + i] = (uint32_t)(n + i), item_key[n + i] = ikey[i];
+    const uint64_t sl = soff[n + i + 1] - soff[n + i];
+    if (sl) memcpy(text.data() + soff[n + i], itx_str_ptr(*x, i, ITX_SIGNATURE), sl);
+  }
+  bv_batch hb = {};
+  hb.n_msgs = N;
+  hb.msg_bytes = bodies.data();
+  hb.msg_off = moff.data();
+  hb.n_keys = (uint32_t)K;
+  hb.key_bytes = kb.data();
+  hb.key_off = koff.data();
+  hb.n_items = N;
+  hb.item_msg = item_msg.data();
+  hb.item_key = item_key.data();
+  const bv_sig_text htext{soff.data(), text.data()};
+  if (!bv_small_batch(ctx, &hb, true)) return BV_OK;
+  int rc = bv_validate_host_batch(ctx, &hb, true);
+  if (rc != BV_OK) return rc;
+  std::vector<uint8_t> h(N * 32), st(N);
+  bv_result r2 = {h.data(), st.data(), nullptr};
+  rc = bv_small_verify(ctx, &hb, &r2, &htext);
+  if (rc != BV_OK) return rc;
+  if (res->msg_hash) memcpy(res->msg_hash, h.data(), n * 32);
+  if (out && out->itx_hash) memcpy(out->itx_hash, h.data() + n * 32, m * 32);
+  compose_host(x, st.data(), force.data(), res, out);
+  *taken = true;
+  return BV_OK;
+}
+
+int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out, bool *no_itx) {
+  bv_host_call call;
+  call.t0 = std::chrono::steady_clock::now();
+  const bv_event_batch *eb = &x->events;
+  const uint64_t n = eb->n_events;
+  if (eb->itx_off || eb->itx_json)
+    return bv_fail(ctx, BV_E_ARGS, "events.itx_off / itx_json must be NULL (the ITXs come from fields)");
+  if (n && !eb->sig_text) return bv_fail(ctx, BV_E_ARGS, "events.sig_text is required");
+  if (const char *why = check_itx(x, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
+  const uint64_t m = x->itx_start[n], N = n + m;
+  if (m == 0) {  // bv_verify_events over nil / "[]" fragments (the caller, outside the lock): it validates the events
+    *no_itx = true;
+    return BV_OK;
+  }
+  int rc = bv_validate_events(ctx, eb);
+  if (rc != BV_OK) return rc;
+  hipStream_t st = ctx->stream;
+  ctx->timing = bv_timing{};
+  ctx->last = st;
+
+  // DAG levels over in-batch parents (refs point backwards: one pass), as bv_verify_events
+  std::vector<uint32_t> level, order, level_off;
+  const bool dag = memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n) != nullptr;
+  if (dag) {
+    level.assign(n, 0);
+    uint32_t nl = 1;
+    for (uint64_t e = 0; e < n; e++) {
+      uint32_t l = 0;
+      for (int p = 0; p < 2; p++)
+        if (eb->parent_kind[2 * e + p] == BV_PARENT_EVENT) l = std::max(l, level[eb->parent_ref[2 * e + p]] + 1);
+      level[e] = l;
+      nl = std::max(nl, l + 1);
+    }
+    level_off.assign(nl + 1, 0);
+    for (uint64_t e = 0; e < n; e++) level_off[level[e] + 1]++;
+    for (uint32_t l = 0; l < nl; l++) level_off[l + 1] += level_off[l];
+    order.resize(n);
+    std::vector<uint32_t> fill(level_off.begin(), level_off.end() - 1);
+    for (uint64_t e = 0; e < n; e++) order[fill[level[e]]++] = (uint32_t)e;
+  }
+
+  // the ITX keys: decoded at a fixed stride by the pool, then packed behind
+  // the creators' keys, one slot per DISTINCT key: an ITX whose key equals a
+  // creator's or an earlier ITX's names that slot (a SyncResponse's ITXs are
+  // about a few peers: the batch keeps its per-key tables and key-cache hits)
+  const uint32_t n_keys = eb->n_keys;
+  if ((uint64_t)n_keys + m > 0xFFFFFFFFull) return bv_fail(ctx, BV_E_ARGS, "more than 2^32 keys");
+  const uint64_t ev_key_len = eb->key_off[n_keys];
+  std::vector<uint8_t> kfix(m * kItxKeyMax), klen(m), force(m);
+  par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
+    std::vector<uint8_t> big;
+    for (uint64_t i = lo; i < hi; i++) {
+      const int64_t k = decode_key(x, i, kfix.data() + i * kItxKeyMax, big);
+      force[i] = k < 0;
+      klen[i] = k < 0 ? 0 : (uint8_t)k;
+    }
+    return true;
+  });
+  std::vector<uint64_t> koff(eb->key_off, eb->key_off + n_keys + 1);
+  std::vector<uint32_t> ikey(m), usrc;  // ITX i's key slot; the ITX whose bytes fill slot n_keys + u
+  {
+    std::unordered_map<std::string, uint32_t> slot;
+    for (uint32_t k = 0; k < n_keys; k++)
+      slot.emplace(koff[k + 1] > koff[k] ? std::string((const char *)eb->key_bytes + koff[k], koff[k + 1] - koff[k])
+                                         : std::string(),
+                   k);
+    for (uint64_t i = 0; i < m; i++) {
+      const auto ins = slot.emplace(std::string((const char *)kfix.data() + i * kItxKeyMax, klen[i]),
+                                    (uint32_t)(n_keys + usrc.size()));
+      if (ins.second) {
+        usrc.push_back((uint32_t)i);
+        koff.push_back(koff.back() + klen[i]);
+      }
+      ikey[i] = ins.first->second;
+    }
+  }
+  const uint64_t K = (uint64_t)n_keys + usrc.size();
+  const uint64_t key_len = koff[K];
+
+  // the signature text: the events', then the ITXs' Signature strings
+  const uint64_t ev_text_len = eb->sig_off[n];
+  std::vector<uint64_t> soff(N + 1);
+  memcpy(soff.data(), eb->sig_off, (n + 1) * 8);
+  for (uint64_t i = 0; i < m; i++) soff[n + i + 1] = soff[n + i] + itx_str_len(*x, i, ITX_SIGNATURE);
+  const uint64_t text_len = soff[N];
+
+  if (ctx->small_path && N <= std::max(ctx->small_max, ctx->small_warm_max)) {
+    bool taken = false;
+    rc = small_route(ctx, x, res, out, dag, order, level_off, koff, kfix, ikey, usrc, force, soff, &taken);
+    if (rc != BV_OK || taken) return rc;
+  }
+
+  // staging layout (pinned host and HBM)
+  const uint64_t n_tx = eb->tx_start[n], tx_len = n_tx ? eb->tx_off[n_tx] : 0;
+  const uint64_t bsig_len = eb->bsig_off ? eb->bsig_off[n] : 0;
+  const uint64_t str_len = x->itx_str_off[4 * m];
+  const uint64_t n_ph = eb->parent_hashes ? eb->n_parent_hashes : 0;
+  size_t total = 0;
+  auto at = [&](size_t bytes, size_t pad = 0) {
+    const size_t o = total;
+    total += align256(bytes + pad);
+    return o;
+  };
+  const size_t o_koff = at((K + 1) * 8), o_kb = at(key_len, 64), keys_end = total;
+  const size_t o_soff = at((N + 1) * 8), o_text = at(text_len, 64), s_end = total;
+  const size_t o_ik = at(N * 4);
+  const size_t o_is = at((n + 1) * 8), o_iln = at(x->itx_list_nil ? n : 0), o_ity = at(m);
+  const size_t o_iso = at((4 * m + 1) * 8), o_istr = at(str_len, 64), o_force = at(m);
+  const bool bulk = !dag;  // the event fields cross only when the device builds the bodies
+  const size_t o_ix = at(bulk ? n * 8 : 0), o_ts = at(bulk ? n * 8 : 0), o_pk = at(bulk ? n * 2 : 0);
+  const size_t o_pr = at(bulk ? n * 16 : 0), o_ph = at(bulk ? n_ph * 32 : 0), o_txs = at(bulk ? (n + 1) * 8 : 0);
+  const size_t o_txo = at(bulk && n_tx ? (n_tx + 1) * 8 : 0), o_txb = at(bulk ? tx_len : 0, 64);
+  const size_t o_tln = at(bulk && eb->tx_list_nil ? n : 0), o_txn = at(bulk && eb->tx_nil ? n_tx : 0);
+  const size_t o_bo = at(bulk && eb->bsig_off ? (n + 1) * 8 : 0), o_bj = at(bulk ? bsig_len : 0);
+  const size_t in_end = total;
+  const size_t o_dig = at(dag ? n * 32 : 0);  // (pinned side only: the host's digests)
+  // device side only: k_ev_compose's outputs
+  const size_t o_evst = at(n), o_dby = at(n * 4), o_bits = at((n + 63) / 64 * 8), o_ist = at(m);
+
+  if (bv_wait_all(ctx) != BV_OK) return BV_E_LAUNCH;  // previous calls' work buffers / staging
+  HIPCHK(ctx->pin_in.ensure(total), BV_E_OOM, "alloc pinned staging");
+  HIPCHK(ctx->d_in.ensure(total), BV_E_OOM, "alloc device staging");
+  HIPCHK(ctx->ev_iota.ensure(N * 4), BV_E_OOM, "alloc item index");
+  uint8_t *pin = (uint8_t *)ctx->pin_in.p, *dev = ctx->d_in.as<uint8_t>();
+  hipStream_t cs = bv_copy_stream(ctx);
+  if (!cs) return bv_fail(ctx, BV_E_NODEVICE, "copy stream");
+  hipEvent_t *ev = ctx->S().ev;
+  HIPCHK(hipEventRecord(ev[E_CALL], cs), BV_E_LAUNCH, "event");
+  auto put = [&](size_t o, const void *src, size_t bytes) {
+    if (bytes && src) ctx->pool->copy(pin + o, src, bytes);
+  };
+  auto h2d = [&](size_t a, size_t z) -> int {
+    if (z > a) HIPCHK(hipMemcpyAsync(dev + a, pin + a, z - a, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
+    return BV_OK;
+  };
+
+  // the keys
+  put(o_koff, koff.data(), (K + 1) * 8);
+  put(o_kb, eb->key_bytes, ev_key_len);
+  for (size_t u = 0; u < usrc.size(); u++) {
+    const uint64_t a = koff[n_keys + u], len = koff[n_keys + u + 1] - a;
+    if (len) memcpy(pin + o_kb + a, kfix.data() + (size_t)usrc[u] * kItxKeyMax, len);
+  }
+  memset(pin + o_kb + key_len, 0, 64);
+  if ((rc = h2d(0, keys_end)) != BV_OK) return rc;
+  HIPCHK(hipEventRecord(ev[E_KREADY], cs), BV_E_LAUNCH, "event");
+
+  // item e: event e under its creator's key; item n + i: ITX i under its key's slot
+  uint32_t *h_ik = (uint32_t *)(pin + o_ik);
+  memcpy(h_ik, eb->creator, n * 4);
+  for (uint64_t i = 0; i < m; i++) h_ik[n + i] = ikey[i];
+
+  bv_batch vb = {};
+  vb.n_msgs = N;
+  vb.n_keys = (uint32_t)K;
+  vb.key_bytes = dev + o_kb;
+  vb.key_off = (const uint64_t *)(dev + o_koff);
+  vb.n_items = N;
+  vb.item_msg = ctx->ev_iota.as<uint32_t>();
+  vb.item_key = (const uint32_t *)(dev + o_ik);
+  bool kc = false;
+  if ((ctx->flags & BV_F_KEY_CACHE) && K <= kKcMaxBatchKeys) {
+    HIPCHK(hipStreamWaitEvent(st, ev[E_KREADY], 0), BV_E_LAUNCH, "join");
+    bv_kc_items items;
+    items.n_items = N;
+    items.h_item_key = h_ik;
+    rc = bv_kc_prepare(ctx, (uint32_t)K, pin + o_kb, (const uint64_t *)(pin + o_koff), vb.key_bytes, vb.key_off, st,
+                       &kc, false, &items);
+    if (rc != BV_OK) return rc;
+  }
+
+  // the signature text: r, s and pre of every item decoded on the device
+  put(o_soff, soff.data(), (N + 1) * 8);
+  put(o_text, eb->sig_text, ev_text_len);
+  par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      const uint64_t len = soff[n + i + 1] - soff[n + i];
+      if (len) memcpy(pin + o_text + soff[n + i], itx_str_ptr(*x, i, ITX_SIGNATURE), len);
+    }
+    return true;
+  });
+  memset(pin + o_text + text_len, 0, 64);
+  if ((rc = h2d(keys_end, s_end)) != BV_OK) return rc;
+  HIPCHK(hipEventRecord(ev[E_SREADY], cs), BV_E_LAUNCH, "event");
+  bv_sig_out so;
+  rc = bv_sig_decode_on_device(ctx, N, (const uint64_t *)(dev + o_soff), dev + o_text, ev[E_SREADY], &so);
+  if (rc != BV_OK) return rc;
+  vb.r_be = so.r, vb.s_be = so.s, vb.pre = so.pre;
+  rc = bv_run_keys(ctx, &vb, ev[E_KREADY], ev[E_SREADY], kc);
+  if (rc != BV_OK) return rc;
+
+  // the fields
+  put(o_is, x->itx_start, (n + 1) * 8);
+  if (x->itx_list_nil) put(o_iln, x->itx_list_nil, n);
+  put(o_ity, x->itx_type, m);
+  put(o_iso, x->itx_str_off, (4 * m + 1) * 8);
+  put(o_istr, x->itx_str, str_len);
+  memset(pin + o_istr + str_len, 0, 64);
+  put(o_force, force.data(), m);
+  if (bulk) {
+    put(o_ix, eb->index, n * 8);
+    put(o_ts, eb->timestamp, n * 8);
+    put(o_pk, eb->parent_kind, n * 2);
+    put(o_pr, eb->parent_ref, n * 16);
+    put(o_ph, eb->parent_hashes, n_ph * 32);
+    put(o_txs, eb->tx_start, (n + 1) * 8);
+    if (n_tx) put(o_txo, eb->tx_off, (n_tx + 1) * 8);
+    put(o_txb, eb->tx_bytes, tx_len);
+    memset(pin + o_txb + tx_len, 0, 64);
+    if (eb->tx_list_nil) put(o_tln, eb->tx_list_nil, n);
+    if (eb->tx_nil) put(o_txn, eb->tx_nil, n_tx);
+    if (eb->bsig_off) put(o_bo, eb->bsig_off, (n + 1) * 8);
+    put(o_bj, eb->bsig_json, bsig_len);
+  }
+  if ((rc = h2d(s_end, in_end)) != BV_OK) return rc;
+  HIPCHK(hipEventRecord(ev[E_SMALL], cs), BV_E_LAUNCH, "event");
+  HIPCHK(hipStreamWaitEvent(st, ev[E_SMALL], 0), BV_E_LAUNCH, "join");
+  HIPCHK(hipStreamWaitEvent(st, ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");
+  HIPCHK(bvk::iota(st, N, ctx->ev_iota.as<uint32_t>()), BV_E_LAUNCH, "k_iota");
+  HIPCHK(hipEventRecord(ev[E_FORK], st), BV_E_LAUNCH, "event");
+
+  // the same batch over device pointers (the serialisers read nothing else)
+  bv_event_itx_batch dx = {};
+  dx.events.n_events = n;
+  dx.events.n_keys = n_keys;
+  dx.events.key_off = (const uint64_t *)(dev + o_koff);  // (the creators' keys lead the combined array)
+  dx.events.key_bytes = dev + o_kb;
+  dx.events.creator = (const uint32_t *)(dev + o_ik);
+  dx.itx_start = (const uint64_t *)(dev + o_is);
+  dx.itx_list_nil = x->itx_list_nil ? dev + o_iln : nullptr;
+  dx.itx_type = dev + o_ity;
+  dx.itx_str_off = (const uint64_t *)(dev + o_iso);
+  dx.itx_str = dev + o_istr;
+  if (bulk) {
+    bv_event_batch &d = dx.events;
+    d.index = (const int64_t *)(dev + o_ix);
+    d.timestamp = (const int64_t *)(dev + o_ts);
+    d.parent_kind = dev + o_pk;
+    d.parent_ref = (const uint64_t *)(dev + o_pr);
+    d.n_parent_hashes = n_ph;
+    d.parent_hashes = n_ph ? dev + o_ph : nullptr;
+    d.tx_start = (const uint64_t *)(dev + o_txs);
+    d.tx_off = n_tx ? (const uint64_t *)(dev + o_txo) : nullptr;
+    d.tx_bytes = dev + o_txb;
+    d.tx_list_nil = eb->tx_list_nil ? dev + o_tln : nullptr;
+    d.tx_nil = eb->tx_nil && n_tx ? dev + o_txn : nullptr;
+    d.bsig_off = eb->bsig_off ? (const uint64_t *)(dev + o_bo) : nullptr;
+    d.bsig_json = dev + o_bj;
+  }
+
+  bv_item_pipe pipe{ctx, &vb, {}, st, kc};
+  rc = bv_out_bufs(ctx, &vb, nullptr, nullptr, nullptr, true, &pipe.o);
+  if (rc != BV_OK) return rc;
+  uint32_t *dig = pipe.o.dig;
+  HIPCHK(bvk::itx_body_hash(st, dx, m, n, dig), BV_E_LAUNCH, "k_itx_body_hash");
+  if (bulk) {
+    HIPCHK(bvk::ev_body_hash_itx(st, dx, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_itx");
+  } else {
+    // the host's part, beside the device's key / s^-1 work and the ITX hashing
+    const HostParFor pf = [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
+      ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
+        fn(lo, hi);
+        return true;
+      });
+    };
+    bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, ctx->dag_scratch,
+                         pin + o_dig);
+    HIPCHK(hipMemcpyAsync(dig, pin + o_dig, n * 32, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d digests");
+  }
+  HIPCHK(hipEventRecord(ev[E_STAGED], cs), BV_E_LAUNCH, "event");
+  call.ms_prep = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - call.t0).count();
+  HIPCHK(hipStreamWaitEvent(st, ev[E_STAGED], 0), BV_E_LAUNCH, "join digests");
+  HIPCHK(hipEventRecord(ev[E_SHA], st), BV_E_LAUNCH, "event");
+  HIPCHK(hipEventRecord(ev[E_HASHED], st), BV_E_LAUNCH, "event");
+  rc = pipe.finish();  // every item: the events' and the ITXs'
+  if (rc != BV_OK) return rc;
+  HIPCHK(bvk::ev_compose(st, n, dx.itx_start, pipe.o.status, dev + o_force, dev + o_evst, (uint32_t *)(dev + o_dby),
+                         (uint64_t *)(dev + o_bits), dev + o_ist),
+         BV_E_LAUNCH, "k_ev_compose");
+
+  // results: the digests (events, then ITXs), then k_ev_compose's outputs as they lie in HBM, in one copy
+  const size_t p_st = align256(N * 32), p_bits = p_st + (o_bits - o_evst), p_dby = p_st + (o_dby - o_evst),
+               p_ist = p_st + (o_ist - o_evst), fold_len = o_ist + align256(m) - o_evst;
+  HIPCHK(ctx->pin_out.ensure(p_st + fold_len + 256), BV_E_OOM, "alloc pinned results");
+  uint8_t *pout = (uint8_t *)ctx->pin_out.p;
+  call.pout = pout;
+  call.o_st = p_st;
+  call.o_bits = p_bits;
+  HIPCHK(hipMemcpyAsync(pout, dig, N * 32, hipMemcpyDeviceToHost, st), BV_E_LAUNCH, "d2h digests");
+  HIPCHK(hipMemcpyAsync(pout + p_st, dev + o_evst, fold_len, hipMemcpyDeviceToHost, st), BV_E_LAUNCH,
+         "d2h statuses, bits, decided_by");
+  HIPCHK(hipEventRecord(ev[E_OUT], st), BV_E_LAUNCH, "event");
+  rc = bv_mark_done(ctx, st);
+  if (rc != BV_OK) return rc;
+  bv_batch sizes = {};
+  sizes.n_msgs = n;
+  sizes.n_items = n;
+  rc = bv_host_finish(ctx, &sizes, res, &call, true);
+  if (rc != BV_OK) return rc;
+  if (out) {
+    if (out->itx_hash) memcpy(out->itx_hash, pout + n * 32, m * 32);
+    if (out->itx_status) memcpy(out->itx_status, pout + p_ist, m);
+    if (out->decided_by) memcpy(out->decided_by, pout + p_dby, n * 4);
+  }
+  return BV_OK;
+}
+
+void lens_scan(uint64_t n, uint64_t *off) {
+  for (uint64_t i = 0; i < n; i++) off[i + 1] += off[i];
+}
+
+}  // namespace
+
+extern "C" int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out) {
+  if (!ctx || !x || !res) return BV_E_ARGS;
+  bool no_itx = false;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
+    const int rc = verify_impl(ctx, x, res, out, &no_itx);
+    if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
+    if (!no_itx) return BV_OK;
+  }
+  // no ITX at all: bv_verify_events over the same events, a nil list as the
+  // empty fragment (null) and an empty non-nil one as "[]"
+  bv_event_batch evb = x->events;
+  const uint64_t n = evb.n_events;
+  std::vector<uint64_t> frag_off;
+  std::vector<uint8_t> frag;
+  const bool all_nil = n == 0 || (x->itx_list_nil && !memchr(x->itx_list_nil, 0, n));
+  if (!all_nil) {
+    frag_off.resize(n + 1);
+    frag_off[0] = 0;
+    for (uint64_t e = 0; e < n; e++) frag_off[e + 1] = frag_off[e] + (itx_list_is_nil(*x, e) ? 0 : 2);
+    frag.resize(frag_off[n]);
+    for (uint64_t i = 0; i < frag.size(); i += 2) frag[i] = '[', frag[i + 1] = ']';
+    evb.itx_off = frag_off.data();
+    evb.itx_json = frag.data();
+  }
+  const int rc = bv_verify_events(ctx, &evb, res);
+  if (rc == BV_OK && out && out->decided_by) memset(out->decided_by, 0xFF, n * 4);  // BV_EV_SELF
+  return rc;
+}
+
+extern "C" int bv_itx_body_lens(const bv_event_itx_batch *x, uint64_t *off) {
+  if (!x || !off) return BV_E_ARGS;
+  if (check_itx(x, nullptr)) return BV_E_ARGS;
+  const uint64_t m = x->itx_start[x->events.n_events];
+  off[0] = 0;
+  for (uint64_t i = 0; i < m; i++) off[i + 1] = itx_body_len(*x, i);
+  lens_scan(m, off);
+  return BV_OK;
+}
+
+extern "C" int bv_itx_bodies(const bv_event_itx_batch *x, const uint64_t *off, uint8_t *out) {
+  if (!x || !off) return BV_E_ARGS;
+  if (check_itx(x, nullptr)) return BV_E_ARGS;
+  const uint64_t m = x->itx_start[x->events.n_events];
+  for (uint64_t i = 0; i < m; i++)
+    if (off[i] > off[i + 1] || off[i + 1] - off[i] < itx_body_len(*x, i)) return BV_E_ARGS;
+  if (m && off[m] > off[0] && !out) return BV_E_ARGS;
+  for (uint64_t i = 0; i < m; i++) {
+    EvjMem o{out + off[i]};
+    itx_body_emit(*x, i, o);
+  }
+  return BV_OK;
+}
+
+extern "C" int bv_event_itx_body_lens(const bv_event_itx_batch *x, uint64_t *off) {
+  if (!x || !off) return BV_E_ARGS;
+  if (check_event_fields(&x->events) || check_itx(x, nullptr)) return BV_E_ARGS;
+  const uint64_t n = x->events.n_events;
+  off[0] = 0;
+  uint32_t pp[2];
+  for (uint64_t e = 0; e < n; e++) off[e + 1] = evj_len(*x, e, pp);
+  lens_scan(n, off);
+  return BV_OK;
+}
+
+extern "C" int bv_event_itx_bodies(const bv_event_itx_batch *x, const uint64_t *off, uint8_t *out) {
+  if (!x || !off) return BV_E_ARGS;
+  if (check_event_fields(&x->events) || check_itx(x, nullptr)) return BV_E_ARGS;
+  const uint64_t n = x->events.n_events;
+  uint32_t pp[2];
+  for (uint64_t e = 0; e < n; e++)
+    if (off[e] > off[e + 1] || off[e + 1] - off[e] < evj_len(*x, e, pp)) return BV_E_ARGS;
+  if (n && off[n] > off[0] && !out) return BV_E_ARGS;
+  for (uint64_t e = 0; e < n; e++) evj_write(*x, e, out + off[e]);
+  return BV_OK;
+}

@@ -45,6 +45,15 @@ hipError_t blk_body_hash(hipStream_t st, const bv_block_batch &b, uint64_t b0, u
 // count[item_block[i]] += 1 for every item whose status is BV_ACCEPT (count zeroed by the caller)
 hipError_t blk_tally(hipStream_t st, uint64_t n_items, const uint32_t *item_block, const uint8_t *status,
                      uint32_t *count);
+// bv_verify_events_itx (itx_kernels.hip, itxjson.h; device pointers in x): InternalTransactionBody.Marshal() of
+// every ITX built and hashed, one lane per ITX, ITX i's digest at message n_ev + i
+hipError_t itx_body_hash(hipStream_t st, const bv_event_itx_batch &x, uint64_t n_itx, uint64_t n_ev, uint32_t *dig);
+// ev_body_hash with the InternalTransactions member built from the ITXs' fields
+hipError_t ev_body_hash_itx(hipStream_t st, const bv_event_itx_batch &x, uint64_t e0, uint64_t e1, uint32_t *dig);
+// Event.Verify's fold over the items (item e: event e, item n_ev + i: ITX i) and the forced-panic flags
+hipError_t ev_compose(hipStream_t st, uint64_t n_ev, const uint64_t *itx_start, const uint8_t *item_status,
+                      const uint8_t *force_panic, uint8_t *ev_status, uint32_t *decided_by, uint64_t *bits,
+                      uint8_t *itx_status);
 hipError_t iota(hipStream_t, uint64_t, uint32_t *);
 hipError_t sig_decode(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be, uint8_t *s_be,
                       uint8_t *pre);

@@ -129,7 +129,10 @@ DEV uint64_t evj_frag_len(const uint64_t *off, uint64_t e) {
 // Body length of event e and the offsets of its in-batch parents' 64 hex
 // characters within the body (EVJ_NOPOS when that parent is not an event
 // of the batch).
-DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
+// (in two parts, so that itxjson.h can put an InternalTransactions member
+// built from fields between them: evj_len_txs is everything before that
+// member's value, evj_len_rest everything after it, `n` the bytes so far)
+DEV uint64_t evj_len_txs(const bv_event_batch &b, uint64_t e) {
   uint64_t n = EVJ_LEN(EVJ_L0);
   if (b.tx_list_nil && b.tx_list_nil[e]) {
     n += 4;
@@ -139,9 +142,10 @@ DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
     for (uint64_t t = t0; t < t1; t++)
       n += (b.tx_nil && b.tx_nil[t]) ? 4 : 2 + evj_b64_len(b.tx_off[t + 1] - b.tx_off[t]);
   }
-  n += EVJ_LEN(EVJ_L1);
-  const uint64_t il = evj_frag_len(b.itx_off, e);
-  n += il ? il : 4;
+  return n + EVJ_LEN(EVJ_L1);
+}
+
+DEV uint64_t evj_len_rest(const bv_event_batch &b, uint64_t e, uint64_t n, uint32_t ppos[2]) {
   n += EVJ_LEN(EVJ_L2);
   for (int p = 0; p < 2; p++) {
     const uint8_t k = b.parent_kind[2 * e + p];
@@ -157,6 +161,11 @@ DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
   n += EVJ_LEN(EVJ_L5) + (bl ? bl : 4);
   n += EVJ_LEN(EVJ_L6) + evj_dec_len(b.timestamp[e]) + 2;  // "}\n"
   return n;
+}
+
+DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
+  const uint64_t il = evj_frag_len(b.itx_off, e);
+  return evj_len_rest(b, e, evj_len_txs(b, e) + (il ? il : 4), ppos);
 }
 
 // Bases of a shard (bv_group_verify_events): the arrays of `b` are the
@@ -180,9 +189,10 @@ struct EvjNoBases {
 
 // Event e's body into sink `o` (evj_len bytes).  In-batch parents get 64 '0'
 // placeholders, overwritten by evj_hex32 once the parent's digest exists.
+// (in two parts around the InternalTransactions member's value, as evj_len;
+// `e` is already the slice's index, e - bs.ev)
 template <class O, class B = EvjNoBases>
-DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
-  e -= bs.ev;
+DEV void evj_emit_txs(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
   evj_lit(o, EVJ_L0);
   if (b.tx_list_nil && b.tx_list_nil[e]) {
     evj_lit(o, "null");
@@ -202,12 +212,10 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) 
     o.put(']');
   }
   evj_lit(o, EVJ_L1);
-  const uint64_t il = evj_frag_len(b.itx_off, e);
-  if (il) {
-    for (uint64_t i = 0; i < il; i++) o.put(b.itx_json[b.itx_off[e] - bs.itx + i]);
-  } else {
-    evj_lit(o, "null");
-  }
+}
+
+template <class O, class B = EvjNoBases>
+DEV void evj_emit_rest(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
   evj_lit(o, EVJ_L2);
   for (int p = 0; p < 2; p++) {
     const uint8_t k = b.parent_kind[2 * e + p];
@@ -245,6 +253,19 @@ DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) 
   evj_dec(o, b.timestamp[e]);
   o.put('}');
   o.put('\n');
+}
+
+template <class O, class B = EvjNoBases>
+DEV void evj_emit(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
+  e -= bs.ev;
+  evj_emit_txs(b, e, o, bs);
+  const uint64_t il = evj_frag_len(b.itx_off, e);
+  if (il) {
+    for (uint64_t i = 0; i < il; i++) o.put(b.itx_json[b.itx_off[e] - bs.itx + i]);
+  } else {
+    evj_lit(o, "null");
+  }
+  evj_emit_rest(b, e, o, bs);
 }
 
 // Streaming SHA-256 sink (k_ev_body_hash: the body is never stored).

@@ -13,11 +13,15 @@
 
 #include <string.h>
 
-#include "evjson.h"
+#include "itxjson.h"
 #include "hostsha.h"
 
-void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
-                      const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
+namespace {
+// X: bv_event_batch (the InternalTransactions member from the verbatim
+// fragment) or bv_event_itx_batch (from the fields, itxjson.h); b: its events
+template <class X>
+void dag_hash(const X &x, const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off,
+              uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
   const uint64_t n = b.n_events;
   if (n == 0) return;
   w.off.assign(n + 1, 0);
@@ -26,13 +30,13 @@ void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint
   uint64_t *off = w.off.data();
   uint32_t *ppos = w.ppos.data();
   pf(n, 512, [&](uint64_t lo, uint64_t hi) {
-    for (uint64_t e = lo; e < hi; e++) off[e + 1] = evj_len(b, e, ppos + 2 * e);
+    for (uint64_t e = lo; e < hi; e++) off[e + 1] = evj_len(x, e, ppos + 2 * e);
   });
   for (uint64_t e = 0; e < n; e++) off[e + 1] += off[e];
   w.bodies.resize(off[n] + 64);
   uint8_t *bodies = w.bodies.data();
   pf(n, 256, [&](uint64_t lo, uint64_t hi) {
-    for (uint64_t e = lo; e < hi; e++) evj_write(b, e, bodies + off[e]);
+    for (uint64_t e = lo; e < hi; e++) evj_write(x, e, bodies + off[e]);
   });
   // level 0: whole digests; above: midstates of the parent-independent blocks
   const uint64_t n0 = level_off[1];
@@ -84,4 +88,15 @@ void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint
     else
       finish(a, z);
   }
+}
+}  // namespace
+
+void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
+                      const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
+  dag_hash(b, b, order, level_off, n_levels, pf, w, digests);
+}
+
+void bv_host_dag_hash_itx(const bv_event_itx_batch &x, const uint32_t *order, const uint32_t *level_off,
+                          uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
+  dag_hash(x, x.events, order, level_off, n_levels, pf, w, digests);
 }

@@ -27,3 +27,7 @@ struct HostDagScratch {
 // level) as bv_events.cpp computes them; writes the n 32-byte digests.
 void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
                       const HostParFor &pf, HostDagScratch &w, uint8_t *digests);
+// The same with the InternalTransactions member built from the ITXs' fields
+// (bv_verify_events_itx, itxjson.h): the ITX text precedes the parents' hex.
+void bv_host_dag_hash_itx(const bv_event_itx_batch &x, const uint32_t *order, const uint32_t *level_off,
+                          uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests);

@@ -15,6 +15,11 @@ Parents follow Hashgraph.ReadWireInfo (hashgraph.go:1540-1595): None -> ""
 InternalTransactions / BlockSignatures are given as their encoding/json
 fragments (b"" = nil -> null); the ITX signatures themselves are verified
 through bv_verify_batch items (Event.Verify's ITX loop), not here.
+
+Or the InternalTransactions as objects (add_event(..., itxs=[...])) and
+pack_itx(): a PackedEventItxBatch for Verifier.verify_events_itx
+(bv_verify_events_itx), which builds and hashes the ITX JSON on the device,
+verifies the ITX signatures too and folds them per event as Event.Verify does.
 """
 from __future__ import annotations
 
@@ -119,6 +124,8 @@ class EventBatchBuilder:
         self._key_idx = {}
         self._ev = []
         self._hashes: List[bytes] = []
+        self._itxs: List[Optional[list]] = []
+        self._sig_text: List[Optional[bytes]] = []
 
     def add_key(self, pub: bytes) -> int:
         pub = bytes(pub)
@@ -130,9 +137,13 @@ class EventBatchBuilder:
 
     def add_event(self, creator: int, index: int, timestamp: int, parents: Sequence[Parent],
                   transactions: Optional[Sequence[Optional[bytes]]], signature, itx_json: bytes = b"",
-                  bsig_json: bytes = b"") -> int:
+                  bsig_json: bytes = b"", itxs: Optional[Sequence] = None) -> int:
         """`signature`: the Event.Signature text (decoded as
-        keys.DecodeSignature) or a (pre, r_be, s_be) tuple."""
+        keys.DecodeSignature) or a (pre, r_be, s_be) tuple.  `itxs`: the
+        event's InternalTransactions as objects (Body.Type, Body.Peer.NetAddr
+        / PubKeyHex / Moniker, Signature; None = a nil slice, [] = an empty
+        one) for pack_itx(), which needs every signature as text and no
+        itx_json."""
         kinds, refs = [], []
         for p in parents:
             if p is None:
@@ -149,6 +160,8 @@ class EventBatchBuilder:
             pre, r, s = signature
         else:
             pre, r, s = native.decode_signature(signature)
+        self._itxs.append(None if itxs is None else list(itxs))
+        self._sig_text.append(None if isinstance(signature, tuple) else _go_bytes(signature))
         self._ev.append((creator, index, timestamp, kinds, refs,
                          None if transactions is None else [None if t is None else bytes(t) for t in transactions],
                          bytes(itx_json), bytes(bsig_json), pre, r, s))
@@ -191,6 +204,112 @@ class EventBatchBuilder:
             r_be=np.frombuffer(b"".join(e[9] for e in self._ev), np.uint8).reshape(n, 32).copy(),
             s_be=np.frombuffer(b"".join(e[10] for e in self._ev), np.uint8).reshape(n, 32).copy(),
             pre=np.array([e[8] for e in self._ev], np.uint8))
+
+
+    def pack_itx(self) -> "PackedEventItxBatch":
+        """The events with their InternalTransactions as fields
+        (bv_event_itx_batch): the event signatures as text, the ITXs' four
+        strings as raw bytes."""
+        if any(t is None for t in self._sig_text):
+            raise ValueError("pack_itx needs every event signature as text")
+        if any(e[6] for e in self._ev):
+            raise ValueError("pack_itx takes the ITXs as objects (itxs=), not as itx_json")
+        n = len(self._ev)
+        sig_off = np.zeros(n + 1, np.uint64)
+        sig_off[1:] = np.cumsum([len(t) for t in self._sig_text], dtype=np.uint64)
+        ev = self.pack().with_signature_text(np.frombuffer(b"".join(self._sig_text), np.uint8).copy(), sig_off)
+        flat = [t for l in self._itxs for t in (l or [])]
+        itx_start = np.zeros(n + 1, np.uint64)
+        itx_start[1:] = np.cumsum([len(l or []) for l in self._itxs], dtype=np.uint64)
+        strs = [_go_bytes(x) for t in flat
+                for x in (t.Body.Peer.NetAddr, t.Body.Peer.PubKeyHex, t.Body.Peer.Moniker, t.Signature)]
+        str_off = np.zeros(len(strs) + 1, np.uint64)
+        str_off[1:] = np.cumsum([len(x) for x in strs], dtype=np.uint64)
+        return PackedEventItxBatch(
+            events=ev, itx_start=itx_start,
+            itx_list_nil=np.array([l is None for l in self._itxs], np.uint8)
+            if any(l is None for l in self._itxs) else None,
+            itx_type=np.array([int(t.Body.Type) & 0xFF for t in flat], np.uint8), itx_str_off=str_off,
+            itx_str=np.frombuffer(b"".join(strs), np.uint8).copy())
+
+
+def _go_bytes(s) -> bytes:
+    """A Go string's bytes (a str is its UTF-8; lone surrogates escape raw bytes)."""
+    return s.encode("utf-8", "surrogateescape") if isinstance(s, str) else bytes(s)
+
+
+class BvEventItxBatch(ctypes.Structure):
+    P = ctypes.c_void_p
+    _fields_ = [("events", BvEventBatch), ("itx_start", P), ("itx_list_nil", P), ("itx_type", P),
+                ("itx_str_off", P), ("itx_str", P)]
+
+
+class BvEventItxOut(ctypes.Structure):
+    _fields_ = [("itx_hash", ctypes.c_void_p), ("itx_status", ctypes.c_void_p), ("decided_by", ctypes.c_void_p)]
+
+
+EV_ITX_INVALID = 4      # BV_EV_ITX_INVALID
+EV_SELF = 0xFFFFFFFF    # BV_EV_SELF
+
+
+@dataclass
+class PackedEventItxBatch:
+    """bv_event_itx_batch: an EventWireBatch (signature text, no itx_json) and
+    the InternalTransactions of its events as fields."""
+    events: EventWireBatch
+    itx_start: np.ndarray                # u64 [n + 1]
+    itx_list_nil: Optional[np.ndarray]   # u8 [n] or None (no nil list)
+    itx_type: np.ndarray                 # u8 [n_itx]
+    itx_str_off: np.ndarray              # u64 [4 * n_itx + 1]
+    itx_str: np.ndarray                  # u8
+
+    @property
+    def n_events(self) -> int:
+        return self.events.n_events
+
+    @property
+    def n_itx(self) -> int:
+        return len(self.itx_type)
+
+    def c_struct(self, keep: list) -> BvEventItxBatch:
+        def p(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a).astype(dt, copy=False))
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        b = BvEventItxBatch()
+        b.events = self.events.c_struct(keep)
+        b.itx_start, b.itx_list_nil = p(self.itx_start, np.uint64), p(self.itx_list_nil, np.uint8)
+        b.itx_type, b.itx_str_off = p(self.itx_type, np.uint8), p(self.itx_str_off, np.uint64)
+        b.itx_str = p(self.itx_str, np.uint8)
+        return b
+
+    def _bodies(self, lens_fn, bodies_fn, n) -> List[bytes]:
+        keep: list = []
+        cb = self.c_struct(keep)
+        off = np.zeros(n + 1, np.uint64)
+        rc = lens_fn(ctypes.byref(cb), off.ctypes.data)
+        if rc != native.BV_OK:
+            raise native.BvError(rc, "body lengths")
+        out = np.zeros(max(int(off[n]), 1), np.uint8)
+        rc = bodies_fn(ctypes.byref(cb), off.ctypes.data, out.ctypes.data)
+        if rc != native.BV_OK:
+            raise native.BvError(rc, "bodies")
+        raw = out.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def itx_bodies(self) -> List[bytes]:
+        """bv_itx_bodies: InternalTransactionBody.Marshal() of every ITX (host only)."""
+        L = native.lib()
+        return self._bodies(L.bv_itx_body_lens, L.bv_itx_bodies, self.n_itx)
+
+    def event_bodies(self) -> List[bytes]:
+        """bv_event_itx_bodies: EventBody.Marshal() of every event, an
+        in-batch parent's hash as 64 '0' (host only)."""
+        L = native.lib()
+        return self._bodies(L.bv_event_itx_body_lens, L.bv_event_itx_bodies, self.n_events)
 
 
 def wire_bytes(b: EventWireBatch) -> int:

@@ -21,6 +21,7 @@ Batch entry points (what the cgo shim in INTEGRATION.md exposes to Go):
 from __future__ import annotations
 
 import math
+import re
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -328,10 +329,15 @@ def verify_itxs(itxs: Sequence[InternalTransaction], verifier=None, text: bool =
     return out
 
 
-def verify_events(events: Sequence[Event], verifier=None) -> List[Outcome]:
+def verify_events(events: Sequence[Event], verifier=None, fields: bool = False) -> List[Outcome]:
     """Event.Verify for every event in one device batch.  Each event's digest
     is stored in its `_hash` (so Hex() does not hash again, cf. the second
-    JSON+SHA-256 in initEventCoordinates, hashgraph.go:474-479)."""
+    JSON+SHA-256 in initEventCoordinates, hashgraph.go:474-479).
+    fields=True: nothing is serialised here; the events and their
+    InternalTransactions go to the library as fields and ONE
+    bv_verify_events_itx call builds, hashes, verifies and folds them."""
+    if fields:
+        return _verify_events_fields(events, verifier)
     bb = BatchBuilder()
     plan = []  # per event: ([itx item or None], event item, msg index)
     for ev in events:
@@ -346,6 +352,55 @@ def verify_events(events: Sequence[Event], verifier=None) -> List[Outcome]:
         itx_st = [None if k is None else int(res.status[k]) for k in itx_items]
         out.append(compose_event_outcome(itx_st, int(res.status[item]),
                                          [t.Signature for t in (ev.Body.InternalTransactions or [])], ev.Signature))
+    return out
+
+
+_EVENT_HEX = re.compile(r"0X[0-9A-F]{64}")
+
+
+def event_itx_outcome(status: int, decided_by: int, itxs: Sequence[InternalTransaction], event_sig="") -> Outcome:
+    """One event of bv_verify_events_itx as Go's Event.Verify result: the
+    folded status and the event-local index of the deciding ITX (EV_SELF: the
+    event signature).  The error texts are compose_event_outcome's."""
+    from .events import EV_ITX_INVALID, EV_SELF
+
+    if decided_by == EV_SELF:
+        return _item_outcome(status, event_sig)
+    itx = itxs[decided_by]
+    if status == EV_ITX_INVALID:
+        return Outcome(False, "invalid signature on internal transaction")
+    if status == REF_PANIC and len(_go_bytes(itx.Body.Peer.PubKeyHex)) < 2:
+        return Outcome(False, "slice bounds out of range", panic=True)
+    return _item_outcome(status, itx.Signature)
+
+
+def _go_bytes(s) -> bytes:
+    return s.encode("utf-8", "surrogateescape") if isinstance(s, str) else bytes(s)
+
+
+def _verify_events_fields(events: Sequence[Event], verifier=None) -> List[Outcome]:
+    from .events import EventBatchBuilder
+
+    if not events:
+        return []
+    eb = EventBatchBuilder()
+    for ev in events:
+        b = ev.Body
+        ps = b.Parents
+        if ps is None or len(ps) != 2 or any(p != "" and not _EVENT_HEX.fullmatch(p) for p in ps):
+            raise ValueError("fields=True needs two parents, each \"\" or an Event.Hex()")
+        if b.Creator is None:
+            raise ValueError("fields=True needs a non-nil Creator")
+        par = [None if p == "" else ("hash", bytes.fromhex(p[2:])) for p in ps]
+        eb.add_event(eb.add_key(b.Creator), b.Index, b.Timestamp, par, b.Transactions, ev.Signature,
+                     bsig_json=b"" if b.BlockSignatures is None else J.slice_(b.BlockSignatures, lambda t: t.json()),
+                     itxs=b.InternalTransactions)
+    res = (verifier or default_verifier()).verify_events_itx(eb.pack_itx())
+    out = []
+    for i, ev in enumerate(events):
+        ev._hash = res.msg_hash[i].tobytes()
+        out.append(event_itx_outcome(int(res.status[i]), int(res.decided_by[i]), ev.Body.InternalTransactions or [],
+                                     ev.Signature))
     return out
 
 

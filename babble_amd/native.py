@@ -40,6 +40,7 @@ EXPORTS = (
     "bv_group_verify_events", "bv_group_kc_register", "bv_plan_event_shards",
     "bv_kc_small_tables", "bv_verify_batch_text", "bv_decode_signatures",
     "bv_verify_blocks", "bv_block_body_lens", "bv_block_bodies",
+    "bv_verify_events_itx", "bv_itx_body_lens", "bv_itx_bodies", "bv_event_itx_body_lens", "bv_event_itx_bodies",
 )
 
 
@@ -176,6 +177,14 @@ def lib() -> ctypes.CDLL:
     L.bv_group_get_timing.restype = ctypes.c_int
     L.bv_verify_events.argtypes = [P, P, ctypes.POINTER(BvResult)]
     L.bv_verify_events.restype = ctypes.c_int
+    L.bv_verify_events_itx.argtypes = [P, P, ctypes.POINTER(BvResult), P]
+    L.bv_verify_events_itx.restype = ctypes.c_int
+    for f in (L.bv_itx_body_lens, L.bv_event_itx_body_lens):
+        f.argtypes = [P, P]
+        f.restype = ctypes.c_int
+    for f in (L.bv_itx_bodies, L.bv_event_itx_bodies):
+        f.argtypes = [P, P, P]
+        f.restype = ctypes.c_int
     L.bv_peer_set_hash.argtypes = [P, ctypes.c_uint32, P, P, P]
     L.bv_peer_set_hash.restype = ctypes.c_int
     L.bv_sync.argtypes = [P]

@@ -35,7 +35,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 from . import gojson as J
 from .hashgraph import (BlockSignature, Event, EventBody, InternalTransaction, Outcome, Peer, DecodeFromString,
-                        EncodeToString, _item_outcome, default_verifier, verify_events, verify_itxs)
+                        EncodeToString, _item_outcome, default_verifier, event_itx_outcome, verify_events,
+                        verify_itxs)
 
 
 @dataclass
@@ -239,13 +240,16 @@ _HEX_RE = re.compile(r"0X[0-9A-F]{64}")
 
 def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int, Peer],
                        participant_event: ParticipantEvent,
-                       verifier=None) -> Tuple[List[Event], List[Outcome], Optional[str]]:
+                       verifier=None, fields: bool = False) -> Tuple[List[Event], List[Outcome], Optional[str]]:
     """sync_verify with the bodies built ON THE DEVICE (bv_verify_events): the
     resolved wire fields cross PCIe, the device serializes every EventBody,
     hashes the in-batch DAG level by level (narrow levels in one launch) and
     verifies every signature; events carrying InternalTransactions get their
     ITX items verified in one more bv_verify_batch (Event.Verify's order,
     event.go:222-230).  Same results as sync_verify (tests/test_sync.py).
+    fields=True: the InternalTransactions cross as fields too and ONE
+    bv_verify_events_itx call verifies and folds them (no ITX JSON on the
+    host, no second call).
     Falls back to sync_verify if a store hash is not a canonical Event.Hex()."""
     from .events import EventBatchBuilder
 
@@ -266,11 +270,12 @@ def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int,
         bs = we.BlockSignatures(cb)
         bsigs.append(bs)
         eb.add_event(eb.add_key(cb), we.Body.Index, we.Body.Timestamp, par, we.Body.Transactions, we.Signature,
-                     itx_json=b"" if itxs is None else J.slice_(itxs, lambda t: t.json()),
-                     bsig_json=b"" if bs is None else J.slice_(bs, lambda t: t.json()))
-    res = v.verify_events(eb.pack())
+                     itx_json=b"" if itxs is None or fields else J.slice_(itxs, lambda t: t.json()),
+                     bsig_json=b"" if bs is None else J.slice_(bs, lambda t: t.json()),
+                     itxs=itxs if fields else None)
+    res = v.verify_events_itx(eb.pack_itx()) if fields else v.verify_events(eb.pack())
     digests = [res.msg_hash[i].tobytes() for i in range(n)]
-    itx_events = [i for i in range(n) if wevents[i].Body.InternalTransactions]
+    itx_events = [] if fields else [i for i in range(n) if wevents[i].Body.InternalTransactions]
     itx_out = {}
     if itx_events:
         flat = [t for i in itx_events for t in wevents[i].Body.InternalTransactions]
@@ -290,6 +295,10 @@ def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int,
                                   Timestamp=we.Body.Timestamp), Signature=we.Signature)
         ev._hash = digests[i]
         events.append(ev)
+        if fields:
+            outcomes.append(event_itx_outcome(int(res.status[i]), int(res.decided_by[i]),
+                                              we.Body.InternalTransactions or [], we.Signature))
+            continue
         o = _item_outcome(int(res.status[i]), we.Signature)
         for io in itx_out.get(i, []):  # event.go:222-230: the first ITX failure wins
             if not io.ok or io.panic:

@@ -35,6 +35,17 @@ class BlockVerifyResult(VerifyResult):
     valid_count: Optional[np.ndarray] = None  # [n_blocks] u32
 
 
+@dataclass
+class EventItxVerifyResult(VerifyResult):
+    """verify_events_itx: msg_hash / status / accept_bits per event (status is
+    the whole of Event.Verify, 4 = an ITX signature was invalid), plus every
+    ITX's body hash and own status and, per event, the event-local index of
+    the ITX that decided it (events.EV_SELF: the event signature did)."""
+    itx_hash: Optional[np.ndarray] = None    # [n_itx, 32] u8
+    itx_status: Optional[np.ndarray] = None  # [n_itx] u8
+    decided_by: Optional[np.ndarray] = None  # [n_events] u32
+
+
 def _p(a: np.ndarray) -> int:
     return a.ctypes.data if a is not None and a.size else 0
 
@@ -260,6 +271,26 @@ class Verifier:
         r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
         self._check(self._L.bv_verify_events(self._ctx, ctypes.byref(cb), ctypes.byref(r)))
         return res
+
+    def verify_events_itx(self, xb) -> "EventItxVerifyResult":
+        """bv_verify_events_itx over an events.PackedEventItxBatch: the whole
+        of Event.Verify (the ITXs from their fields, then the event signature)
+        in one call."""
+        from .events import BvEventItxOut
+
+        keep: list = []
+        cb = xb.c_struct(keep)
+        n, m = xb.n_events, xb.n_itx
+        h = np.zeros((max(n, 1), 32), np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        bits = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        ih = np.zeros((max(m, 1), 32), np.uint8)
+        ist = np.zeros(max(m, 1), np.uint8)
+        by = np.zeros(max(n, 1), np.uint32)
+        res = native.BvResult(h.ctypes.data, st.ctypes.data, bits.ctypes.data)
+        out = BvEventItxOut(ih.ctypes.data, ist.ctypes.data, by.ctypes.data)
+        self._check(self._L.bv_verify_events_itx(self._ctx, ctypes.byref(cb), ctypes.byref(res), ctypes.byref(out)))
+        return EventItxVerifyResult(h[:n], st[:n], bits[: (n + 63) // 64], ih[:m], ist[:m], by[:n])
 
     def peer_set_hash(self, pubkeys: Sequence[bytes]) -> bytes:
         """bv_peer_set_hash: PeerSet.Hash over the peers' key bytes (b"" for
@@ -587,6 +618,13 @@ class PinnedArena:
             a = getattr(eb, f.name)
             out[f.name] = None if a is None else self.copy(np.asarray(a).astype(dt.get(f.name, a.dtype), copy=False))
         return type(eb)(**out)
+
+    def event_itx_batch(self, xb):
+        """The same events.PackedEventItxBatch with every array in pinned memory."""
+        return type(xb)(events=self.wire(xb.events), itx_start=self.copy(xb.itx_start.astype(np.uint64)),
+                        itx_list_nil=None if xb.itx_list_nil is None else self.copy(xb.itx_list_nil),
+                        itx_type=self.copy(xb.itx_type), itx_str_off=self.copy(xb.itx_str_off.astype(np.uint64)),
+                        itx_str=self.copy(xb.itx_str))
 
     def close(self):
         for p in self._blocks:

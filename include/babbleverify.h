@@ -306,7 +306,8 @@ int bv_sync(bv_ctx *ctx);
  * event signature (keys.Verify as composed by Event.Verify, event.go:232-247).
  * InternalTransactions are serialized from the verbatim fragment but their
  * own signatures are NOT verified here (use bv_verify_batch items, as the Go
- * shim does for Event.Verify's ITX loop). */
+ * shim does for Event.Verify's ITX loop), or pass the ITXs' fields to
+ * bv_verify_events_itx below, which verifies them in the same call). */
 #define BV_PARENT_NONE 0  /* "" (wire index < 0)                              */
 #define BV_PARENT_HASH 1  /* known hash: parent_ref indexes parent_hashes     */
 #define BV_PARENT_EVENT 2 /* an earlier event of this batch: parent_ref = its
@@ -352,6 +353,62 @@ typedef struct {
  * the batch, an out-of-range key / hash / offset).  As for bv_verify_batch,
  * arrays and result buffers in bv_host_alloc memory are DMA'd in place. */
 int bv_verify_events(bv_ctx *ctx, const bv_event_batch *events, bv_result *result);
+
+/* The whole of Event.Verify (event.go:219-247) in one call: the events as
+ * above, and their InternalTransactions from FIELDS instead of a JSON
+ * fragment.  The library builds each InternalTransactionBody.Marshal() and
+ * each element of EventBody.InternalTransactions on the device (Go 1.13
+ * encoding/json string escaping included), hashes them, verifies every ITX
+ * signature (InternalTransaction.Verify, internal_transaction.go:139-154) and
+ * the event signature, and folds them in Event.Verify's order: the first ITX
+ * of an event that is not ACCEPT decides it (REJECT_ERR -> BV_REJECT_ERR,
+ * REF_PANIC -> BV_REF_PANIC, REJECT -> BV_EV_ITX_INVALID), else the event
+ * signature's class does.  An ITX whose PubKeyHex is shorter than 2 bytes is
+ * BV_REF_PANIC whatever its Signature is (Go panics in PubKeyBytes before
+ * DecodeSignature runs).
+ * result: per event, as bv_verify_events; msg_hash holds the event body
+ * digests (written for every event, also one whose ITX fails), status the
+ * fold, accept_bits bit e = status[e] == BV_ACCEPT.
+ * BV_E_ARGS (with a bv_last_error text): everything bv_verify_events rejects;
+ * events.itx_off or events.itx_json non-NULL; events.sig_text NULL; itx_start
+ * NULL, not starting at 0 or not monotone; itx_str_off NULL while n_itx > 0,
+ * not starting at 0 or not monotone; itx_str NULL while bytes are named;
+ * itx_type NULL while n_itx > 0; n_events + n_itx > 2^32.  n_itx == 0 is
+ * valid and returns exactly what bv_verify_events returns for the same events
+ * with nil or "[]" fragments.
+ * Single device only: bv_group_verify_events takes no ITX fields. */
+#define BV_EV_ITX_INVALID 4 /* (false, "invalid signature on internal transaction") */
+#define BV_EV_SELF 0xFFFFFFFFu
+typedef struct {
+  bv_event_batch events;       /* itx_off / itx_json must be NULL; sig_text / sig_off required */
+  const uint64_t *itx_start;   /* n_events + 1: event e owns ITXs [itx_start[e], itx_start[e+1]) */
+  const uint8_t *itx_list_nil; /* per event, 1: the slice is nil -> null (NULL: none; an empty
+                                  non-nil list is []), exactly as tx_list_nil */
+  const uint8_t *itx_type;     /* per ITX: Body.Type */
+  const uint64_t *itx_str_off; /* 4 * n_itx + 1 offsets into itx_str, per ITX in the order
+                                  NetAddr, PubKeyHex, Moniker, Signature (raw Go string bytes) */
+  const uint8_t *itx_str;
+} bv_event_itx_batch;
+
+typedef struct {        /* every pointer may be NULL */
+  uint8_t *itx_hash;    /* 32 * n_itx: InternalTransactionBody.Hash */
+  uint8_t *itx_status;  /* n_itx: the ITX's own InternalTransaction.Verify class, 0..3 */
+  uint32_t *decided_by; /* n_events: BV_EV_SELF, or the event-local index of the ITX whose
+                           failure is the event's outcome */
+} bv_event_itx_out;
+
+int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *batch, bv_result *result, bv_event_itx_out *out);
+/* The serialiser's public form (host only, no device; as bv_block_body_lens /
+ * bv_block_bodies): off[i + 1] - off[i] = the length of body i, off[0] = 0;
+ * then the bodies at out + off[i] (each at least as long as the length).
+ * bv_itx_*: InternalTransactionBody.Marshal() of every ITX; bv_event_itx_*:
+ * EventBody.Marshal() of every event, an in-batch parent's hash as 64 '0'.
+ * Only the fields the serialiser reads are checked.  BV_E_ARGS on a NULL
+ * pointer or malformed offsets. */
+int bv_itx_body_lens(const bv_event_itx_batch *batch, uint64_t *off /* n_itx + 1 */);
+int bv_itx_bodies(const bv_event_itx_batch *batch, const uint64_t *off, uint8_t *out);
+int bv_event_itx_body_lens(const bv_event_itx_batch *batch, uint64_t *off /* n_events + 1 */);
+int bv_event_itx_bodies(const bv_event_itx_batch *batch, const uint64_t *off, uint8_t *out);
 
 /* Multi-GPU: one verifier over several devices of this process (one bv_ctx
  * per device, the caller's device ordinals).  bv_group_verify_batch shards
