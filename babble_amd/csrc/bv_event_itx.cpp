@@ -16,13 +16,22 @@
 // text (the events' followed by the ITXs' Signature strings: k_sig_decode,
 // s^-1), then the fields.  A batch without ITXs is bv_verify_events over the
 // same events with nil / "[]" fragments.
+//
+// bv_verify_events_fields is the same driver over a bv_event_fields_batch
+// (`f` below, null for bv_verify_events_itx): the BlockSignatures member comes
+// from fields too (bsigjson.h), so the bodies are built by that batch's
+// evj_len / evj_emit on all three routes (k_ev_body_hash_fields, the host DAG,
+// the one-launch small path), the block-signature fields are staged beside the
+// others, and a batch without ITX fields (ev.itx_start == NULL) or without
+// ITXs runs the same pipeline over n_events items.  The block signatures are
+// hashed, not verified.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "bv_internal.h"
 #include "hostsha.h"
-#include "itxjson.h"
+#include "bsigjson.h"
 
 #define HIPCHK(expr, code, what)                               \
   do {                                                         \
@@ -63,6 +72,30 @@ const char *check_itx(const bv_event_itx_batch *x, CopyPool *pool) {
   if (!monotone(pool, x->itx_str_off, 4 * m)) return "itx_str_off not monotone";
   if (x->itx_str_off[4 * m] && !x->itx_str) return "null itx_str";
   return nullptr;
+}
+
+// bsig_check (bsigjson.h) with the offset scans spread over the pool
+const char *check_bsig(const bv_event_fields_batch *f, CopyPool *pool) {
+  return bsig_check(*f, [pool](const uint64_t *off, uint64_t n) { return monotone(pool, off, n); });
+}
+
+// a fields batch stages bsig_val_off / bsig_val_bytes only when an entry reads them
+bool bsig_has_bytes(const bv_event_fields_batch *f, uint64_t nb) {
+  return f->bsig_val_kind && nb && memchr(f->bsig_val_kind, BV_BSIG_VAL_BYTES, nb);
+}
+
+// Event e's body by the batch's own serialiser: f's when there is one
+uint64_t body_len(const bv_event_itx_batch *x, const bv_event_fields_batch *f, uint64_t e, uint32_t pp[2]) {
+  return f ? evj_len(*f, e, pp) : evj_len(*x, e, pp);
+}
+void body_write(const bv_event_itx_batch *x, const bv_event_fields_batch *f, uint64_t e, uint8_t *o) {
+  if (f) evj_write(*f, e, o);
+  else evj_write(*x, e, o);
+}
+void dag_hash(const bv_event_itx_batch *x, const bv_event_fields_batch *f, const std::vector<uint32_t> &order,
+              const std::vector<uint32_t> &level_off, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
+  if (f) bv_host_dag_hash_fields(*f, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, w, digests);
+  else bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, w, digests);
 }
 
 // The event fields the serialiser reads, without a context (the host
@@ -118,7 +151,7 @@ void compose_host(const bv_event_itx_batch *x, const uint8_t *item_status, const
   for (uint64_t e = 0; e < n; e++) {
     uint8_t st = item_status[e];
     uint32_t by = BV_EV_SELF;
-    const uint64_t i0 = x->itx_start[e], i1 = x->itx_start[e + 1];
+    const uint64_t i0 = x->itx_start ? x->itx_start[e] : 0, i1 = x->itx_start ? x->itx_start[e + 1] : 0;
     for (uint64_t i = i0; i < i1; i++) {
       const uint8_t c = force[i] ? (uint8_t)BV_REF_PANIC : item_status[n + i];
       if (out && out->itx_status) out->itx_status[i] = c;
@@ -139,13 +172,14 @@ void compose_host(const bv_event_itx_batch *x, const uint8_t *item_status, const
 // which leaves the bodies with their parents' hex spliced in), that path hashes
 // them on the host (hostsha) and verifies the items in one launch, and the
 // fold is done on the host.  *taken = false: the bulk pipeline's.
-int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out, bool dag,
+int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
+                bv_event_itx_out *out, bool dag,
                 const std::vector<uint32_t> &order, const std::vector<uint32_t> &level_off,
                 const std::vector<uint64_t> &koff, const std::vector<uint8_t> &kfix,
                 const std::vector<uint32_t> &ikey, const std::vector<uint32_t> &usrc,
                 const std::vector<uint8_t> &force, const std::vector<uint64_t> &soff, bool *taken) {
   const bv_event_batch *eb = &x->events;
-  const uint64_t n = eb->n_events, m = x->itx_start[n], N = n + m;
+  const uint64_t n = eb->n_events, m = x->itx_start ? x->itx_start[n] : 0, N = n + m;
   const uint32_t n_keys = eb->n_keys;
   const uint64_t K = (uint64_t)n_keys + usrc.size();
   *taken = false;
@@ -160,18 +194,17 @@ int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
         return true;
       });
     };
-    bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, ctx->dag_scratch,
-                         evdig.data());
+    dag_hash(x, f, order, level_off, pf, ctx->dag_scratch, evdig.data());
     memcpy(moff.data(), ctx->dag_scratch.off.data(), (n + 1) * 8);
   } else {
-    for (uint64_t e = 0; e < n; e++) moff[e + 1] = moff[e] + evj_len(*x, e, pp);
+    for (uint64_t e = 0; e < n; e++) moff[e + 1] = moff[e] + body_len(x, f, e, pp);
   }
   for (uint64_t i = 0; i < m; i++) moff[n + i + 1] = moff[n + i] + itx_body_len(*x, i);
   bodies.resize(moff[N] + 64);
   if (dag) {
     memcpy(bodies.data(), ctx->dag_scratch.bodies.data(), moff[n]);
   } else {
-    for (uint64_t e = 0; e < n; e++) evj_write(*x, e, bodies.data() + moff[e]);
+    for (uint64_t e = 0; e < n; e++) body_write(x, f, e, bodies.data() + moff[e]);
   }
   for (uint64_t i = 0; i < m; i++) {
     EvjMem o{bodies.data() + moff[n + i]};
@@ -216,7 +249,10 @@ int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   return BV_OK;
 }
 
-int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out, bool *no_itx) {
+// f: the same batch with its block signatures as fields (x == &f->ev; checked
+// by the caller, at least one block signature), or null
+int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
+                bv_event_itx_out *out, bool *no_itx) {
   bv_host_call call;
   call.t0 = std::chrono::steady_clock::now();
   const bv_event_batch *eb = &x->events;
@@ -224,9 +260,11 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   if (eb->itx_off || eb->itx_json)
     return bv_fail(ctx, BV_E_ARGS, "events.itx_off / itx_json must be NULL (the ITXs come from fields)");
   if (n && !eb->sig_text) return bv_fail(ctx, BV_E_ARGS, "events.sig_text is required");
-  if (const char *why = check_itx(x, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
-  const uint64_t m = x->itx_start[n], N = n + m;
-  if (m == 0) {  // bv_verify_events over nil / "[]" fragments (the caller, outside the lock): it validates the events
+  const bool itx_fields = !f || x->itx_start;  // (a fields batch may carry no ITX fields at all)
+  if (itx_fields)
+    if (const char *why = check_itx(x, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
+  const uint64_t m = itx_fields ? x->itx_start[n] : 0, N = n + m;
+  if (m == 0 && !f) {  // bv_verify_events over nil / "[]" fragments (the caller, outside the lock): it validates the events
     *no_itx = true;
     return BV_OK;
   }
@@ -265,7 +303,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   if ((uint64_t)n_keys + m > 0xFFFFFFFFull) return bv_fail(ctx, BV_E_ARGS, "more than 2^32 keys");
   const uint64_t ev_key_len = eb->key_off[n_keys];
   std::vector<uint8_t> kfix(m * kItxKeyMax), klen(m), force(m);
-  par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
+  if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
     std::vector<uint8_t> big;
     for (uint64_t i = lo; i < hi; i++) {
       const int64_t k = decode_key(x, i, kfix.data() + i * kItxKeyMax, big);
@@ -302,16 +340,22 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   for (uint64_t i = 0; i < m; i++) soff[n + i + 1] = soff[n + i] + itx_str_len(*x, i, ITX_SIGNATURE);
   const uint64_t text_len = soff[N];
 
-  if (ctx->small_path && N <= std::max(ctx->small_max, ctx->small_warm_max)) {
+  // (the fields entry asks bv_small_batch's own first question ahead of the bodies small_route builds for it:
+  // past small_max only a key-cache context can take the path)
+  if (ctx->small_path && N <= std::max(ctx->small_max, ctx->small_warm_max) &&
+      (!f || N <= ctx->small_max || (ctx->flags & BV_F_KEY_CACHE))) {
     bool taken = false;
-    rc = small_route(ctx, x, res, out, dag, order, level_off, koff, kfix, ikey, usrc, force, soff, &taken);
+    rc = small_route(ctx, x, f, res, out, dag, order, level_off, koff, kfix, ikey, usrc, force, soff, &taken);
     if (rc != BV_OK || taken) return rc;
   }
 
   // staging layout (pinned host and HBM)
   const uint64_t n_tx = eb->tx_start[n], tx_len = n_tx ? eb->tx_off[n_tx] : 0;
   const uint64_t bsig_len = eb->bsig_off ? eb->bsig_off[n] : 0;
-  const uint64_t str_len = x->itx_str_off[4 * m];
+  const uint64_t str_len = m ? x->itx_str_off[4 * m] : 0;
+  const uint64_t nb = f ? f->bsig_start[n] : 0, bs_len = nb ? f->bsig_sig_off[nb] : 0;  // block signatures, as fields
+  const bool bv_bytes = f && bsig_has_bytes(f, nb);
+  const uint64_t bv_len = bv_bytes ? f->bsig_val_off[nb] : 0;
   const uint64_t n_ph = eb->parent_hashes ? eb->n_parent_hashes : 0;
   size_t total = 0;
   auto at = [&](size_t bytes, size_t pad = 0) {
@@ -330,6 +374,11 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   const size_t o_txo = at(bulk && n_tx ? (n_tx + 1) * 8 : 0), o_txb = at(bulk ? tx_len : 0, 64);
   const size_t o_tln = at(bulk && eb->tx_list_nil ? n : 0), o_txn = at(bulk && eb->tx_nil ? n_tx : 0);
   const size_t o_bo = at(bulk && eb->bsig_off ? (n + 1) * 8 : 0), o_bj = at(bulk ? bsig_len : 0);
+  const bool bf = bulk && f;
+  const size_t o_fs = at(bf ? (n + 1) * 8 : 0), o_fln = at(bf && f->bsig_list_nil ? n : 0), o_fix = at(bf ? nb * 8 : 0);
+  const size_t o_fso = at(bf ? (nb + 1) * 8 : 0), o_fsg = at(bf ? bs_len : 0, 64);
+  const size_t o_fk = at(bf && f->bsig_val_kind ? nb : 0), o_fvo = at(bf && bv_bytes ? (nb + 1) * 8 : 0);
+  const size_t o_fvb = at(bf ? bv_len : 0, 64);
   const size_t in_end = total;
   const size_t o_dig = at(dag ? n * 32 : 0);  // (pinned side only: the host's digests)
   // device side only: k_ev_compose's outputs
@@ -344,17 +393,62 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   if (!cs) return bv_fail(ctx, BV_E_NODEVICE, "copy stream");
   hipEvent_t *ev = ctx->S().ev;
   HIPCHK(hipEventRecord(ev[E_CALL], cs), BV_E_LAUNCH, "event");
-  auto put = [&](size_t o, const void *src, size_t bytes) {
-    if (bytes && src) ctx->pool->copy(pin + o, src, bytes);
+  // The fields entry: a large array that lies in bv_host_alloc memory is not
+  // copied into the staging block; the DMA engine reads it where it is (as
+  // bv_verify_events does), and the staging range around it goes in pieces.
+  struct Direct {
+    size_t o;
+    const void *src;
+    size_t n;
+  };
+  constexpr size_t kDirectMin = 256 << 10;
+  std::vector<Direct> directs;
+  // The fields entry's bulk route, a batch of more than one chunk of events:
+  // the arrays that are indexed by event (or by an event's transactions or
+  // block signatures) cross in event-range slices, chunk by chunk, into the
+  // same one-piece device layout, and each chunk's bodies are hashed and its
+  // items verified while the next chunk crosses (as bv_verify_events' chunks).
+  // A sliced array is left out of the one-piece copies (Direct with no source).
+  enum SliceKind { S_ALL, S_EV, S_EVP1, S_TX, S_TXP1, S_TXB, S_BS, S_BSP1, S_BSB, S_BVB };
+  struct Slice {
+    size_t o;
+    const uint8_t *src;
+    size_t elem;
+    int kind;
+    bool direct;
+  };
+  uint64_t chunk_ev = 1 << 17;
+  if (const char *env = getenv("BV_FIELDS_CHUNK")) chunk_ev = std::max<uint64_t>(64, (strtoull(env, nullptr, 10) + 63) / 64 * 64);
+  const bool chunked = f && !dag && n > chunk_ev;
+  std::vector<Slice> slices;
+  auto put = [&](size_t o, const void *src, size_t bytes, int kind = S_ALL, size_t elem = 1) {
+    if (!bytes || !src) return;
+    const bool direct = f && bytes >= kDirectMin && bv_is_pinned(src, bytes);
+    if (chunked && kind != S_ALL) {
+      slices.push_back({o, (const uint8_t *)src, elem, kind, direct});
+      directs.push_back({o, nullptr, bytes});
+    } else if (direct) {
+      directs.push_back({o, src, bytes});
+    } else {
+      ctx->pool->copy(pin + o, src, bytes);
+    }
   };
   auto h2d = [&](size_t a, size_t z) -> int {
-    if (z > a) HIPCHK(hipMemcpyAsync(dev + a, pin + a, z - a, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
+    std::sort(directs.begin(), directs.end(), [](const Direct &x, const Direct &y) { return x.o < y.o; });
+    size_t at = a;
+    for (const Direct &d : directs) {  // (every one lies in [a, z): they are taken out below)
+      if (d.o > at) HIPCHK(hipMemcpyAsync(dev + at, pin + at, d.o - at, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
+      if (d.src) HIPCHK(hipMemcpyAsync(dev + d.o, d.src, d.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d in place");
+      at = d.o + d.n;
+    }
+    directs.clear();
+    if (z > at) HIPCHK(hipMemcpyAsync(dev + at, pin + at, z - at, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
     return BV_OK;
   };
 
   // the keys
   put(o_koff, koff.data(), (K + 1) * 8);
-  put(o_kb, eb->key_bytes, ev_key_len);
+  if (ev_key_len) memcpy(pin + o_kb, eb->key_bytes, ev_key_len);  // (always staged: the key cache reads them here)
   for (size_t u = 0; u < usrc.size(); u++) {
     const uint64_t a = koff[n_keys + u], len = koff[n_keys + u + 1] - a;
     if (len) memcpy(pin + o_kb + a, kfix.data() + (size_t)usrc[u] * kItxKeyMax, len);
@@ -390,7 +484,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   // the signature text: r, s and pre of every item decoded on the device
   put(o_soff, soff.data(), (N + 1) * 8);
   put(o_text, eb->sig_text, ev_text_len);
-  par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
+  if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; i++) {
       const uint64_t len = soff[n + i + 1] - soff[n + i];
       if (len) memcpy(pin + o_text + soff[n + i], itx_str_ptr(*x, i, ITX_SIGNATURE), len);
@@ -408,33 +502,47 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   if (rc != BV_OK) return rc;
 
   // the fields
-  put(o_is, x->itx_start, (n + 1) * 8);
-  if (x->itx_list_nil) put(o_iln, x->itx_list_nil, n);
+  if (itx_fields) put(o_is, x->itx_start, (n + 1) * 8, S_EVP1);
+  if (x->itx_list_nil) put(o_iln, x->itx_list_nil, n, S_EV, 1);
   put(o_ity, x->itx_type, m);
-  put(o_iso, x->itx_str_off, (4 * m + 1) * 8);
+  if (m) put(o_iso, x->itx_str_off, (4 * m + 1) * 8);
   put(o_istr, x->itx_str, str_len);
   memset(pin + o_istr + str_len, 0, 64);
   put(o_force, force.data(), m);
   if (bulk) {
-    put(o_ix, eb->index, n * 8);
-    put(o_ts, eb->timestamp, n * 8);
-    put(o_pk, eb->parent_kind, n * 2);
-    put(o_pr, eb->parent_ref, n * 16);
+    put(o_ix, eb->index, n * 8, S_EV, 8);
+    put(o_ts, eb->timestamp, n * 8, S_EV, 8);
+    put(o_pk, eb->parent_kind, n * 2, S_EV, 2);
+    put(o_pr, eb->parent_ref, n * 16, S_EV, 16);
     put(o_ph, eb->parent_hashes, n_ph * 32);
-    put(o_txs, eb->tx_start, (n + 1) * 8);
-    if (n_tx) put(o_txo, eb->tx_off, (n_tx + 1) * 8);
-    put(o_txb, eb->tx_bytes, tx_len);
+    put(o_txs, eb->tx_start, (n + 1) * 8, S_EVP1);
+    if (n_tx) put(o_txo, eb->tx_off, (n_tx + 1) * 8, S_TXP1);
+    put(o_txb, eb->tx_bytes, tx_len, S_TXB);
     memset(pin + o_txb + tx_len, 0, 64);
-    if (eb->tx_list_nil) put(o_tln, eb->tx_list_nil, n);
-    if (eb->tx_nil) put(o_txn, eb->tx_nil, n_tx);
+    if (eb->tx_list_nil) put(o_tln, eb->tx_list_nil, n, S_EV, 1);
+    if (eb->tx_nil) put(o_txn, eb->tx_nil, n_tx, S_TX, 1);
     if (eb->bsig_off) put(o_bo, eb->bsig_off, (n + 1) * 8);
     put(o_bj, eb->bsig_json, bsig_len);
+  }
+  if (bf) {
+    put(o_fs, f->bsig_start, (n + 1) * 8, S_EVP1);
+    if (f->bsig_list_nil) put(o_fln, f->bsig_list_nil, n, S_EV, 1);
+    put(o_fix, f->bsig_index, nb * 8, S_BS, 8);
+    put(o_fso, f->bsig_sig_off, (nb + 1) * 8, S_BSP1);
+    put(o_fsg, f->bsig_sig, bs_len, S_BSB);
+    memset(pin + o_fsg + bs_len, 0, 64);
+    if (f->bsig_val_kind) put(o_fk, f->bsig_val_kind, nb, S_BS, 1);
+    if (bv_bytes) put(o_fvo, f->bsig_val_off, (nb + 1) * 8, S_BSP1);
+    put(o_fvb, f->bsig_val_bytes, bv_len, S_BVB);
+    memset(pin + o_fvb + bv_len, 0, 64);
   }
   if ((rc = h2d(s_end, in_end)) != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_SMALL], cs), BV_E_LAUNCH, "event");
   HIPCHK(hipStreamWaitEvent(st, ev[E_SMALL], 0), BV_E_LAUNCH, "join");
   HIPCHK(hipStreamWaitEvent(st, ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");
   HIPCHK(bvk::iota(st, N, ctx->ev_iota.as<uint32_t>()), BV_E_LAUNCH, "k_iota");
+  if (!itx_fields)  // no itx_start crossed: k_ev_compose's view of it (no event owns an ITX) is set on the device
+    HIPCHK(hipMemsetAsync(dev + o_is, 0, (n + 1) * 8, st), BV_E_LAUNCH, "zero itx_start");
   HIPCHK(hipEventRecord(ev[E_FORK], st), BV_E_LAUNCH, "event");
 
   // the same batch over device pointers (the serialisers read nothing else)
@@ -444,7 +552,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   dx.events.key_off = (const uint64_t *)(dev + o_koff);  // (the creators' keys lead the combined array)
   dx.events.key_bytes = dev + o_kb;
   dx.events.creator = (const uint32_t *)(dev + o_ik);
-  dx.itx_start = (const uint64_t *)(dev + o_is);
+  dx.itx_start = itx_fields ? (const uint64_t *)(dev + o_is) : nullptr;
   dx.itx_list_nil = x->itx_list_nil ? dev + o_iln : nullptr;
   dx.itx_type = dev + o_ity;
   dx.itx_str_off = (const uint64_t *)(dev + o_iso);
@@ -465,13 +573,63 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
     d.bsig_off = eb->bsig_off ? (const uint64_t *)(dev + o_bo) : nullptr;
     d.bsig_json = dev + o_bj;
   }
+  bv_event_fields_batch df = {};
+  if (bf) {
+    df.ev = dx;
+    df.bsig_start = (const uint64_t *)(dev + o_fs);
+    df.bsig_list_nil = f->bsig_list_nil ? dev + o_fln : nullptr;
+    df.bsig_index = (const int64_t *)(dev + o_fix);
+    df.bsig_sig_off = (const uint64_t *)(dev + o_fso);
+    df.bsig_sig = dev + o_fsg;
+    df.bsig_val_kind = f->bsig_val_kind ? dev + o_fk : nullptr;
+    df.bsig_val_off = bv_bytes ? (const uint64_t *)(dev + o_fvo) : nullptr;
+    df.bsig_val_bytes = dev + o_fvb;
+  }
 
   bv_item_pipe pipe{ctx, &vb, {}, st, kc};
   rc = bv_out_bufs(ctx, &vb, nullptr, nullptr, nullptr, true, &pipe.o);
   if (rc != BV_OK) return rc;
   uint32_t *dig = pipe.o.dig;
   HIPCHK(bvk::itx_body_hash(st, dx, m, n, dig), BV_E_LAUNCH, "k_itx_body_hash");
-  if (bulk) {
+  if (chunked) {
+    for (uint64_t a = 0; a < n; a += chunk_ev) {
+      const uint64_t z = std::min(n, a + chunk_ev);
+      const uint64_t t0 = eb->tx_start[a], t1 = eb->tx_start[z], j0 = f->bsig_start[a], j1 = f->bsig_start[z];
+      std::vector<CopyPool::Piece> pieces;
+      for (const Slice &g : slices) {
+        size_t lo = 0, hi = 0;
+        switch (g.kind) {
+          case S_EV: lo = a * g.elem, hi = z * g.elem; break;
+          case S_EVP1: lo = a * 8, hi = (z + 1) * 8; break;
+          case S_TX: lo = t0 * g.elem, hi = t1 * g.elem; break;
+          case S_TXP1: lo = t0 * 8, hi = (t1 + 1) * 8; break;
+          case S_TXB: lo = eb->tx_off[t0], hi = eb->tx_off[t1]; break;
+          case S_BS: lo = j0 * g.elem, hi = j1 * g.elem; break;
+          case S_BSP1: lo = j0 * 8, hi = (j1 + 1) * 8; break;
+          case S_BSB: lo = f->bsig_sig_off[j0], hi = f->bsig_sig_off[j1]; break;
+          case S_BVB: lo = f->bsig_val_off[j0], hi = f->bsig_val_off[j1]; break;
+        }
+        if (lo >= hi) continue;
+        if (g.direct)
+          HIPCHK(hipMemcpyAsync(dev + g.o + lo, g.src + lo, hi - lo, hipMemcpyHostToDevice, cs), BV_E_LAUNCH,
+                 "h2d (pinned caller buffer)");
+        else
+          pieces.push_back({pin + g.o + lo, g.src + lo, hi - lo});
+      }
+      ctx->pool->copy_many(pieces);  // the rest of the chunk into pinned memory, then its DMA
+      for (const CopyPool::Piece &q : pieces) {
+        const size_t o = (uint8_t *)q.dst - pin;
+        HIPCHK(hipMemcpyAsync(dev + o, pin + o, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
+      }
+      hipEvent_t landed = ctx->chunk_ev[(a / chunk_ev) % ctx->chunk_ev.size()];
+      HIPCHK(hipEventRecord(landed, cs), BV_E_LAUNCH, "event");
+      HIPCHK(hipStreamWaitEvent(st, landed, 0), BV_E_LAUNCH, "join chunk");
+      HIPCHK(bvk::ev_body_hash_fields(st, df, a, z, dig), BV_E_LAUNCH, "k_ev_body_hash_fields");
+      if (z < n && (rc = pipe.upto(z)) != BV_OK) return rc;  // (the last chunk's items: pipe.finish below)
+    }
+  } else if (bf) {
+    HIPCHK(bvk::ev_body_hash_fields(st, df, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_fields");
+  } else if (bulk) {
     HIPCHK(bvk::ev_body_hash_itx(st, dx, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_itx");
   } else {
     // the host's part, beside the device's key / s^-1 work and the ITX hashing
@@ -481,8 +639,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
         return true;
       });
     };
-    bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, ctx->dag_scratch,
-                         pin + o_dig);
+    dag_hash(x, f, order, level_off, pf, ctx->dag_scratch, pin + o_dig);
     HIPCHK(hipMemcpyAsync(dig, pin + o_dig, n * 32, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d digests");
   }
   HIPCHK(hipEventRecord(ev[E_STAGED], cs), BV_E_LAUNCH, "event");
@@ -492,7 +649,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   HIPCHK(hipEventRecord(ev[E_HASHED], st), BV_E_LAUNCH, "event");
   rc = pipe.finish();  // every item: the events' and the ITXs'
   if (rc != BV_OK) return rc;
-  HIPCHK(bvk::ev_compose(st, n, dx.itx_start, pipe.o.status, dev + o_force, dev + o_evst, (uint32_t *)(dev + o_dby),
+  HIPCHK(bvk::ev_compose(st, n, (const uint64_t *)(dev + o_is), pipe.o.status, dev + o_force, dev + o_evst, (uint32_t *)(dev + o_dby),
                          (uint64_t *)(dev + o_bits), dev + o_ist),
          BV_E_LAUNCH, "k_ev_compose");
 
@@ -516,8 +673,8 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_eve
   rc = bv_host_finish(ctx, &sizes, res, &call, true);
   if (rc != BV_OK) return rc;
   if (out) {
-    if (out->itx_hash) memcpy(out->itx_hash, pout + n * 32, m * 32);
-    if (out->itx_status) memcpy(out->itx_status, pout + p_ist, m);
+    if (out->itx_hash && m) memcpy(out->itx_hash, pout + n * 32, m * 32);
+    if (out->itx_status && m) memcpy(out->itx_status, pout + p_ist, m);
     if (out->decided_by) memcpy(out->decided_by, pout + p_dby, n * 4);
   }
   return BV_OK;
@@ -535,7 +692,7 @@ extern "C" int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *x, bv
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
-    const int rc = verify_impl(ctx, x, res, out, &no_itx);
+    const int rc = verify_impl(ctx, x, nullptr, res, out, &no_itx);
     if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
     if (!no_itx) return BV_OK;
   }
@@ -604,5 +761,84 @@ extern "C" int bv_event_itx_bodies(const bv_event_itx_batch *x, const uint64_t *
     if (off[e] > off[e + 1] || off[e + 1] - off[e] < evj_len(*x, e, pp)) return BV_E_ARGS;
   if (n && off[n] > off[0] && !out) return BV_E_ARGS;
   for (uint64_t e = 0; e < n; e++) evj_write(*x, e, out + off[e]);
+  return BV_OK;
+}
+
+// nil -> the empty fragment (null), an empty non-nil list -> "[]": what an
+// entry that takes fragments needs for a member without elements.  nil[e] != 0:
+// event e's list is nil; a NULL array: every list is (null_is_nil) or none is.
+// Leaves *o / *j NULL when every list is nil.
+static void empty_list_fragments(uint64_t n, const uint8_t *nil, bool null_is_nil, std::vector<uint64_t> &off,
+                                 std::vector<uint8_t> &json, const uint64_t **o, const uint8_t **j) {
+  if (!n || (nil ? !memchr(nil, 0, n) : null_is_nil)) return;
+  off.resize(n + 1);
+  off[0] = 0;
+  for (uint64_t e = 0; e < n; e++) off[e + 1] = off[e] + (nil && nil[e] ? 0 : 2);
+  json.resize(off[n]);
+  for (uint64_t i = 0; i < json.size(); i += 2) json[i] = '[', json[i + 1] = ']';
+  *o = off.data();
+  *j = json.data();
+}
+
+extern "C" int bv_verify_events_fields(bv_ctx *ctx, const bv_event_fields_batch *f, bv_result *res,
+                                       bv_event_itx_out *out) {
+  if (!ctx || !f || !res) return BV_E_ARGS;
+  const bv_event_batch *eb = &f->ev.events;
+  const uint64_t n = eb->n_events;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
+    if (eb->itx_off || eb->itx_json)
+      return bv_fail(ctx, BV_E_ARGS, "events.itx_off / itx_json must be NULL (the ITXs come from fields)");
+    if (n && !eb->sig_text) return bv_fail(ctx, BV_E_ARGS, "events.sig_text is required");
+    if (const char *why = check_bsig(f, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
+    if (n && f->bsig_start[n]) {
+      bool unused = false;
+      const int rc = verify_impl(ctx, &f->ev, f, res, out, &unused);
+      return rc == BV_OK ? BV_OK : bv_drain(ctx, ctx->stream, rc);
+    }
+  }
+  // no block signature at all: the entry that takes fragments, over the same
+  // events with nil / "[]" fragments
+  std::vector<uint64_t> boff, ioff;
+  std::vector<uint8_t> bjson, ijson;
+  bv_event_itx_batch xi = f->ev;
+  empty_list_fragments(n, f->bsig_list_nil, false, boff, bjson, &xi.events.bsig_off, &xi.events.bsig_json);
+  if (xi.itx_start) return bv_verify_events_itx(ctx, &xi, res, out);
+  empty_list_fragments(n, f->ev.itx_list_nil, true, ioff, ijson, &xi.events.itx_off, &xi.events.itx_json);
+  const int rc = bv_verify_events(ctx, &xi.events, res);
+  if (rc == BV_OK && out && out->decided_by) memset(out->decided_by, 0xFF, n * 4);  // BV_EV_SELF
+  return rc;
+}
+
+// The fields the serialiser reads, without a context
+static const char *check_fields_host(const bv_event_fields_batch *f) {
+  if (const char *why = check_event_fields(&f->ev.events)) return why;
+  if (f->ev.events.itx_off || f->ev.events.itx_json) return "fragment";
+  if (f->ev.itx_start)
+    if (const char *why = check_itx(&f->ev, nullptr)) return why;
+  return check_bsig(f, nullptr);
+}
+
+extern "C" int bv_event_fields_body_lens(const bv_event_fields_batch *f, uint64_t *off) {
+  if (!f || !off) return BV_E_ARGS;
+  if (check_fields_host(f)) return BV_E_ARGS;
+  const uint64_t n = f->ev.events.n_events;
+  off[0] = 0;
+  uint32_t pp[2];
+  for (uint64_t e = 0; e < n; e++) off[e + 1] = evj_len(*f, e, pp);
+  lens_scan(n, off);
+  return BV_OK;
+}
+
+extern "C" int bv_event_fields_bodies(const bv_event_fields_batch *f, const uint64_t *off, uint8_t *out) {
+  if (!f || !off) return BV_E_ARGS;
+  if (check_fields_host(f)) return BV_E_ARGS;
+  const uint64_t n = f->ev.events.n_events;
+  uint32_t pp[2];
+  for (uint64_t e = 0; e < n; e++)
+    if (off[e] > off[e + 1] || off[e + 1] - off[e] < evj_len(*f, e, pp)) return BV_E_ARGS;
+  if (n && off[n] > off[0] && !out) return BV_E_ARGS;
+  for (uint64_t e = 0; e < n; e++) evj_write(*f, e, out + off[e]);
   return BV_OK;
 }

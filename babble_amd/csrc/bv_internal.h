@@ -54,6 +54,9 @@ hipError_t ev_body_hash_itx(hipStream_t st, const bv_event_itx_batch &x, uint64_
 hipError_t ev_compose(hipStream_t st, uint64_t n_ev, const uint64_t *itx_start, const uint8_t *item_status,
                       const uint8_t *force_panic, uint8_t *ev_status, uint32_t *decided_by, uint64_t *bits,
                       uint8_t *itx_status);
+// ev_body_hash_itx with the BlockSignatures member built from fields too (fields_kernels.hip, bsigjson.h)
+hipError_t ev_body_hash_fields(hipStream_t st, const bv_event_fields_batch &f, uint64_t e0, uint64_t e1,
+                               uint32_t *dig);
 hipError_t iota(hipStream_t, uint64_t, uint32_t *);
 hipError_t sig_decode(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be, uint8_t *s_be,
                       uint8_t *pre);

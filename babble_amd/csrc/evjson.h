@@ -8,8 +8,9 @@
 //    "Creator":"<b64>","Index":<dec>,"BlockSignatures":B,"Timestamp":<dec>}\n
 //   T  nil -> null, else [x,...] with x = null (nil []byte) or "<b64>"
 //      (padded StdEncoding; empty -> "")
-//   I, B  verbatim JSON from the host (encoding/json of the slices; rare in
-//      gossip); an empty fragment means nil -> null
+//   I, B  verbatim JSON from the host (encoding/json of the slices); an empty
+//      fragment means nil -> null.  Or built from fields as well: itxjson.h
+//      (I) and bsigjson.h (B, which most events of a live network carry)
 //   p  "" (no parent, ReadWireInfo index < 0, hashgraph.go:1541-1573) or
 //      "0X" + 64 UPPERCASE hex (Event.Hex, common/hex.go:10-12) of a known
 //      hash or of an EARLIER event of the batch (spliced in when that
@@ -131,7 +132,10 @@ DEV uint64_t evj_frag_len(const uint64_t *off, uint64_t e) {
 // of the batch).
 // (in two parts, so that itxjson.h can put an InternalTransactions member
 // built from fields between them: evj_len_txs is everything before that
-// member's value, evj_len_rest everything after it, `n` the bytes so far)
+// member's value, evj_len_rest everything after it, `n` the bytes so far;
+// evj_len_rest itself in two parts around the BlockSignatures member's value,
+// evj_len_mid and evj_len_tail, so that bsigjson.h can build that member from
+// fields too: the in-batch parents' positions lie before it)
 DEV uint64_t evj_len_txs(const bv_event_batch &b, uint64_t e) {
   uint64_t n = EVJ_LEN(EVJ_L0);
   if (b.tx_list_nil && b.tx_list_nil[e]) {
@@ -145,7 +149,7 @@ DEV uint64_t evj_len_txs(const bv_event_batch &b, uint64_t e) {
   return n + EVJ_LEN(EVJ_L1);
 }
 
-DEV uint64_t evj_len_rest(const bv_event_batch &b, uint64_t e, uint64_t n, uint32_t ppos[2]) {
+DEV uint64_t evj_len_mid(const bv_event_batch &b, uint64_t e, uint64_t n, uint32_t ppos[2]) {
   n += EVJ_LEN(EVJ_L2);
   for (int p = 0; p < 2; p++) {
     const uint8_t k = b.parent_kind[2 * e + p];
@@ -157,10 +161,17 @@ DEV uint64_t evj_len_rest(const bv_event_batch &b, uint64_t e, uint64_t n, uint3
   const uint32_t c = b.creator[e];
   n += EVJ_LEN(EVJ_L3) + evj_b64_len(b.key_off[c + 1] - b.key_off[c]);
   n += EVJ_LEN(EVJ_L4) + evj_dec_len(b.index[e]);
+  return n + EVJ_LEN(EVJ_L5);
+}
+
+DEV uint64_t evj_len_tail(const bv_event_batch &b, uint64_t e, uint64_t n) {
+  return n + EVJ_LEN(EVJ_L6) + evj_dec_len(b.timestamp[e]) + 2;  // "}\n"
+}
+
+DEV uint64_t evj_len_rest(const bv_event_batch &b, uint64_t e, uint64_t n, uint32_t ppos[2]) {
+  n = evj_len_mid(b, e, n, ppos);
   const uint64_t bl = evj_frag_len(b.bsig_off, e);
-  n += EVJ_LEN(EVJ_L5) + (bl ? bl : 4);
-  n += EVJ_LEN(EVJ_L6) + evj_dec_len(b.timestamp[e]) + 2;  // "}\n"
-  return n;
+  return evj_len_tail(b, e, n + (bl ? bl : 4));
 }
 
 DEV uint64_t evj_len(const bv_event_batch &b, uint64_t e, uint32_t ppos[2]) {
@@ -189,8 +200,8 @@ struct EvjNoBases {
 
 // Event e's body into sink `o` (evj_len bytes).  In-batch parents get 64 '0'
 // placeholders, overwritten by evj_hex32 once the parent's digest exists.
-// (in two parts around the InternalTransactions member's value, as evj_len;
-// `e` is already the slice's index, e - bs.ev)
+// (in parts around the InternalTransactions and BlockSignatures members'
+// values, as evj_len; `e` is already the slice's index, e - bs.ev)
 template <class O, class B = EvjNoBases>
 DEV void evj_emit_txs(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
   evj_lit(o, EVJ_L0);
@@ -215,7 +226,7 @@ DEV void evj_emit_txs(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B
 }
 
 template <class O, class B = EvjNoBases>
-DEV void evj_emit_rest(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
+DEV void evj_emit_mid(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
   evj_lit(o, EVJ_L2);
   for (int p = 0; p < 2; p++) {
     const uint8_t k = b.parent_kind[2 * e + p];
@@ -243,16 +254,26 @@ DEV void evj_emit_rest(const bv_event_batch &b, uint64_t e, O &o, const B &bs = 
   evj_lit(o, EVJ_L4);
   evj_dec(o, b.index[e]);
   evj_lit(o, EVJ_L5);
+}
+
+template <class O>
+DEV void evj_emit_tail(const bv_event_batch &b, uint64_t e, O &o) {
+  evj_lit(o, EVJ_L6);
+  evj_dec(o, b.timestamp[e]);
+  o.put('}');
+  o.put('\n');
+}
+
+template <class O, class B = EvjNoBases>
+DEV void evj_emit_rest(const bv_event_batch &b, uint64_t e, O &o, const B &bs = B{}) {
+  evj_emit_mid(b, e, o, bs);
   const uint64_t bl = evj_frag_len(b.bsig_off, e);
   if (bl) {
     for (uint64_t i = 0; i < bl; i++) o.put(b.bsig_json[b.bsig_off[e] - bs.bsig + i]);
   } else {
     evj_lit(o, "null");
   }
-  evj_lit(o, EVJ_L6);
-  evj_dec(o, b.timestamp[e]);
-  o.put('}');
-  o.put('\n');
+  evj_emit_tail(b, e, o);
 }
 
 template <class O, class B = EvjNoBases>

@@ -13,12 +13,14 @@
 
 #include <string.h>
 
-#include "itxjson.h"
+#include "bsigjson.h"
 #include "hostsha.h"
 
 namespace {
 // X: bv_event_batch (the InternalTransactions member from the verbatim
-// fragment) or bv_event_itx_batch (from the fields, itxjson.h); b: its events
+// fragment), bv_event_itx_batch (from the fields, itxjson.h) or
+// bv_event_fields_batch (BlockSignatures from fields too, bsigjson.h); b: its
+// events
 template <class X>
 void dag_hash(const X &x, const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off,
               uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
@@ -99,4 +101,9 @@ void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint
 void bv_host_dag_hash_itx(const bv_event_itx_batch &x, const uint32_t *order, const uint32_t *level_off,
                           uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
   dag_hash(x, x.events, order, level_off, n_levels, pf, w, digests);
+}
+
+void bv_host_dag_hash_fields(const bv_event_fields_batch &f, const uint32_t *order, const uint32_t *level_off,
+                             uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
+  dag_hash(f, f.ev.events, order, level_off, n_levels, pf, w, digests);
 }

@@ -31,3 +31,7 @@ void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint
 // (bv_verify_events_itx, itxjson.h): the ITX text precedes the parents' hex.
 void bv_host_dag_hash_itx(const bv_event_itx_batch &x, const uint32_t *order, const uint32_t *level_off,
                           uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests);
+// The same with the BlockSignatures member built from fields too
+// (bv_verify_events_fields, bsigjson.h): that text follows the parents' hex.
+void bv_host_dag_hash_fields(const bv_event_fields_batch &f, const uint32_t *order, const uint32_t *level_off,
+                             uint32_t n_levels, const HostParFor &pf, HostDagScratch &w, uint8_t *digests);

@@ -186,21 +186,17 @@ DEV bool itx_list_is_nil(const bv_event_itx_batch &x, uint64_t e) { return x.itx
 // The evj_len / evj_emit variants: event e's body with the InternalTransactions
 // member built from the fields (x.events.itx_off is NULL).  ppos: as evj_len,
 // the in-batch parents' hex positions, after the ITX text.
-DEV uint64_t evj_len(const bv_event_itx_batch &x, uint64_t e, uint32_t ppos[2]) {
-  uint64_t n = evj_len_txs(x.events, e);
-  if (itx_list_is_nil(x, e)) {
-    n += 4;
-  } else {
-    const uint64_t i0 = x.itx_start[e], i1 = x.itx_start[e + 1];
-    n += 2 + (i1 > i0 ? i1 - i0 - 1 : 0);
-    for (uint64_t i = i0; i < i1; i++) n += itx_elem_len(x, i);
-  }
-  return evj_len_rest(x.events, e, n, ppos);
+// (the member's value on its own: bsigjson.h builds the rest differently)
+DEV uint64_t itx_list_len(const bv_event_itx_batch &x, uint64_t e) {
+  if (itx_list_is_nil(x, e)) return 4;
+  const uint64_t i0 = x.itx_start[e], i1 = x.itx_start[e + 1];
+  uint64_t n = 2 + (i1 > i0 ? i1 - i0 - 1 : 0);
+  for (uint64_t i = i0; i < i1; i++) n += itx_elem_len(x, i);
+  return n;
 }
 
 template <class O>
-DEV void evj_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
-  evj_emit_txs(x.events, e, o);
+DEV void itx_list_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
   if (itx_list_is_nil(x, e)) {
     evj_lit(o, "null");
   } else {
@@ -212,6 +208,16 @@ DEV void evj_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
     }
     o.put(']');
   }
+}
+
+DEV uint64_t evj_len(const bv_event_itx_batch &x, uint64_t e, uint32_t ppos[2]) {
+  return evj_len_rest(x.events, e, evj_len_txs(x.events, e) + itx_list_len(x, e), ppos);
+}
+
+template <class O>
+DEV void evj_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
+  evj_emit_txs(x.events, e, o);
+  itx_list_emit(x, e, o);
   evj_emit_rest(x.events, e, o);
 }
 

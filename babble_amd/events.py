@@ -20,6 +20,9 @@ Or the InternalTransactions as objects (add_event(..., itxs=[...])) and
 pack_itx(): a PackedEventItxBatch for Verifier.verify_events_itx
 (bv_verify_events_itx), which builds and hashes the ITX JSON on the device,
 verifies the ITX signatures too and folds them per event as Event.Verify does.
+Or the BlockSignatures as objects too (add_event(..., bsigs=[...])) and
+pack_fields(): a PackedEventFieldsBatch for Verifier.verify_events_fields
+(bv_verify_events_fields), the whole Event from fields, no JSON at all.
 """
 from __future__ import annotations
 
@@ -125,6 +128,7 @@ class EventBatchBuilder:
         self._ev = []
         self._hashes: List[bytes] = []
         self._itxs: List[Optional[list]] = []
+        self._bsigs: List[Optional[list]] = []
         self._sig_text: List[Optional[bytes]] = []
 
     def add_key(self, pub: bytes) -> int:
@@ -137,13 +141,15 @@ class EventBatchBuilder:
 
     def add_event(self, creator: int, index: int, timestamp: int, parents: Sequence[Parent],
                   transactions: Optional[Sequence[Optional[bytes]]], signature, itx_json: bytes = b"",
-                  bsig_json: bytes = b"", itxs: Optional[Sequence] = None) -> int:
+                  bsig_json: bytes = b"", itxs: Optional[Sequence] = None, bsigs: Optional[Sequence] = None) -> int:
         """`signature`: the Event.Signature text (decoded as
         keys.DecodeSignature) or a (pre, r_be, s_be) tuple.  `itxs`: the
         event's InternalTransactions as objects (Body.Type, Body.Peer.NetAddr
         / PubKeyHex / Moniker, Signature; None = a nil slice, [] = an empty
         one) for pack_itx(), which needs every signature as text and no
-        itx_json."""
+        itx_json.  `bsigs`: the event's BlockSignatures as objects (Validator
+        bytes or None, Index, Signature; None = a nil slice) for
+        pack_fields(), which takes no bsig_json either."""
         kinds, refs = [], []
         for p in parents:
             if p is None:
@@ -161,6 +167,7 @@ class EventBatchBuilder:
         else:
             pre, r, s = native.decode_signature(signature)
         self._itxs.append(None if itxs is None else list(itxs))
+        self._bsigs.append(None if bsigs is None else list(bsigs))
         self._sig_text.append(None if isinstance(signature, tuple) else _go_bytes(signature))
         self._ev.append((creator, index, timestamp, kinds, refs,
                          None if transactions is None else [None if t is None else bytes(t) for t in transactions],
@@ -231,6 +238,47 @@ class EventBatchBuilder:
             if any(l is None for l in self._itxs) else None,
             itx_type=np.array([int(t.Body.Type) & 0xFF for t in flat], np.uint8), itx_str_off=str_off,
             itx_str=np.frombuffer(b"".join(strs), np.uint8).copy())
+
+
+    def pack_fields(self, itx_fields: Optional[bool] = None) -> "PackedEventFieldsBatch":
+        """The events with every member as fields (bv_event_fields_batch):
+        pack_itx()'s batch and the BlockSignatures given as objects.  A
+        Validator equal to the creator's key bytes is BV_BSIG_VAL_CREATOR,
+        other bytes BV_BSIG_VAL_BYTES, None BV_BSIG_VAL_NIL.  itx_fields:
+        False leaves out the ITX arrays (itx_start NULL; the batch must carry
+        no ITX), None does so when no event has one."""
+        if any(e[7] for e in self._ev):
+            raise ValueError("pack_fields takes the block signatures as objects (bsigs=), not as bsig_json")
+        xb = self.pack_itx()
+        n = len(self._ev)
+        if itx_fields is None:
+            itx_fields = xb.n_itx > 0
+        if not itx_fields:
+            if xb.n_itx:
+                raise ValueError("itx_fields=False with InternalTransactions in the batch")
+            nil = np.array([l is None for l in self._itxs], np.uint8)
+            xb = PackedEventItxBatch(events=xb.events, itx_start=None, itx_list_nil=None if nil.all() else nil,
+                                     itx_type=np.zeros(0, np.uint8), itx_str_off=None, itx_str=np.zeros(0, np.uint8))
+        flat = [(t, self._keys[e[0]]) for e, l in zip(self._ev, self._bsigs) for t in (l or [])]
+        start = np.zeros(n + 1, np.uint64)
+        start[1:] = np.cumsum([len(l or []) for l in self._bsigs], dtype=np.uint64)
+        sigs = [_go_bytes(t.Signature) for t, _ in flat]
+        sig_off = np.zeros(len(flat) + 1, np.uint64)
+        sig_off[1:] = np.cumsum([len(x) for x in sigs], dtype=np.uint64)
+        kind = np.array([BSIG_VAL_NIL if t.Validator is None else BSIG_VAL_CREATOR if bytes(t.Validator) == ck
+                         else BSIG_VAL_BYTES for t, ck in flat], np.uint8)
+        vals = [bytes(t.Validator) if k == BSIG_VAL_BYTES else b"" for (t, _), k in zip(flat, kind)]
+        val_off = np.zeros(len(flat) + 1, np.uint64)
+        val_off[1:] = np.cumsum([len(x) for x in vals], dtype=np.uint64)
+        has_bytes = bool((kind == BSIG_VAL_BYTES).any())
+        return PackedEventFieldsBatch(
+            ev=xb, bsig_start=start,
+            bsig_list_nil=np.array([l is None for l in self._bsigs], np.uint8)
+            if any(l is None for l in self._bsigs) else None,
+            bsig_index=np.array([int(t.Index) for t, _ in flat], np.int64), bsig_sig_off=sig_off,
+            bsig_sig=np.frombuffer(b"".join(sigs), np.uint8).copy(),
+            bsig_val_kind=kind if kind.any() else None, bsig_val_off=val_off if has_bytes else None,
+            bsig_val_bytes=np.frombuffer(b"".join(vals), np.uint8).copy())
 
 
 def _go_bytes(s) -> bytes:
@@ -310,6 +358,72 @@ class PackedEventItxBatch:
         in-batch parent's hash as 64 '0' (host only)."""
         L = native.lib()
         return self._bodies(L.bv_event_itx_body_lens, L.bv_event_itx_bodies, self.n_events)
+
+
+BSIG_VAL_CREATOR, BSIG_VAL_BYTES, BSIG_VAL_NIL = 0, 1, 2   # BV_BSIG_VAL_*
+
+
+class BvEventFieldsBatch(ctypes.Structure):
+    P = ctypes.c_void_p
+    _fields_ = [("ev", BvEventItxBatch), ("bsig_start", P), ("bsig_list_nil", P), ("bsig_index", P),
+                ("bsig_sig_off", P), ("bsig_sig", P), ("bsig_val_kind", P), ("bsig_val_off", P), ("bsig_val_bytes", P)]
+
+
+@dataclass
+class PackedEventFieldsBatch:
+    """bv_event_fields_batch: a PackedEventItxBatch (its itx_start None: no
+    ITX fields) and the BlockSignatures of its events as fields."""
+    ev: PackedEventItxBatch
+    bsig_start: np.ndarray                # u64 [n + 1]
+    bsig_list_nil: Optional[np.ndarray]   # u8 [n] or None (no nil list)
+    bsig_index: np.ndarray                # i64 [n_bsig]
+    bsig_sig_off: np.ndarray              # u64 [n_bsig + 1]
+    bsig_sig: np.ndarray                  # u8
+    bsig_val_kind: Optional[np.ndarray]   # u8 [n_bsig] or None (all the creator's key)
+    bsig_val_off: Optional[np.ndarray]    # u64 [n_bsig + 1] or None (no BSIG_VAL_BYTES entry)
+    bsig_val_bytes: np.ndarray            # u8
+
+    @property
+    def n_events(self) -> int:
+        return self.ev.n_events
+
+    @property
+    def n_itx(self) -> int:
+        return self.ev.n_itx
+
+    @property
+    def n_bsig(self) -> int:
+        return len(self.bsig_index)
+
+    def c_struct(self, keep: list) -> BvEventFieldsBatch:
+        def p(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a).astype(dt, copy=False))
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        b = BvEventFieldsBatch()
+        b.ev = self.ev.c_struct(keep)
+        b.bsig_start, b.bsig_list_nil = p(self.bsig_start, np.uint64), p(self.bsig_list_nil, np.uint8)
+        b.bsig_index, b.bsig_sig_off = p(self.bsig_index, np.int64), p(self.bsig_sig_off, np.uint64)
+        b.bsig_sig, b.bsig_val_kind = p(self.bsig_sig, np.uint8), p(self.bsig_val_kind, np.uint8)
+        b.bsig_val_off, b.bsig_val_bytes = p(self.bsig_val_off, np.uint64), p(self.bsig_val_bytes, np.uint8)
+        return b
+
+    def event_bodies(self) -> List[bytes]:
+        """bv_event_fields_bodies: EventBody.Marshal() of every event, an
+        in-batch parent's hash as 64 '0' (host only)."""
+        L = native.lib()
+        return PackedEventItxBatch._bodies(self, L.bv_event_fields_body_lens, L.bv_event_fields_bodies, self.n_events)
+
+
+def fields_bytes(fb: PackedEventFieldsBatch) -> int:
+    """Bytes of the block-signature fields of this batch (what
+    bv_verify_events_fields stages for them on its bulk path)."""
+    arrs = [fb.bsig_start, fb.bsig_index, fb.bsig_sig_off, fb.bsig_sig, fb.bsig_val_bytes]
+    arrs += [a for a in (fb.bsig_list_nil, fb.bsig_val_kind, fb.bsig_val_off) if a is not None]
+    return int(sum(a.nbytes for a in arrs))
 
 
 def wire_bytes(b: EventWireBatch) -> int:

@@ -335,7 +335,9 @@ def verify_events(events: Sequence[Event], verifier=None, fields: bool = False) 
     JSON+SHA-256 in initEventCoordinates, hashgraph.go:474-479).
     fields=True: nothing is serialised here; the events and their
     InternalTransactions go to the library as fields and ONE
-    bv_verify_events_itx call builds, hashes, verifies and folds them."""
+    bv_verify_events_itx call builds, hashes, verifies and folds them; when
+    an event carries BlockSignatures they go as fields too
+    (bv_verify_events_fields)."""
     if fields:
         return _verify_events_fields(events, verifier)
     bb = BatchBuilder()
@@ -393,9 +395,13 @@ def _verify_events_fields(events: Sequence[Event], verifier=None) -> List[Outcom
             raise ValueError("fields=True needs a non-nil Creator")
         par = [None if p == "" else ("hash", bytes.fromhex(p[2:])) for p in ps]
         eb.add_event(eb.add_key(b.Creator), b.Index, b.Timestamp, par, b.Transactions, ev.Signature,
-                     bsig_json=b"" if b.BlockSignatures is None else J.slice_(b.BlockSignatures, lambda t: t.json()),
-                     itxs=b.InternalTransactions)
-    res = (verifier or default_verifier()).verify_events_itx(eb.pack_itx())
+                     itxs=b.InternalTransactions, bsigs=b.BlockSignatures)
+    v = verifier or default_verifier()
+    # block signatures anywhere: the whole Event as fields; else the call made before there was one
+    if any(ev.Body.BlockSignatures is not None for ev in events):
+        res = v.verify_events_fields(eb.pack_fields(itx_fields=True))
+    else:
+        res = v.verify_events_itx(eb.pack_itx())
     out = []
     for i, ev in enumerate(events):
         ev._hash = res.msg_hash[i].tobytes()

@@ -41,6 +41,7 @@ EXPORTS = (
     "bv_kc_small_tables", "bv_verify_batch_text", "bv_decode_signatures",
     "bv_verify_blocks", "bv_block_body_lens", "bv_block_bodies",
     "bv_verify_events_itx", "bv_itx_body_lens", "bv_itx_bodies", "bv_event_itx_body_lens", "bv_event_itx_bodies",
+    "bv_verify_events_fields", "bv_event_fields_body_lens", "bv_event_fields_bodies",
 )
 
 
@@ -179,10 +180,12 @@ def lib() -> ctypes.CDLL:
     L.bv_verify_events.restype = ctypes.c_int
     L.bv_verify_events_itx.argtypes = [P, P, ctypes.POINTER(BvResult), P]
     L.bv_verify_events_itx.restype = ctypes.c_int
-    for f in (L.bv_itx_body_lens, L.bv_event_itx_body_lens):
+    L.bv_verify_events_fields.argtypes = [P, P, ctypes.POINTER(BvResult), P]
+    L.bv_verify_events_fields.restype = ctypes.c_int
+    for f in (L.bv_itx_body_lens, L.bv_event_itx_body_lens, L.bv_event_fields_body_lens):
         f.argtypes = [P, P]
         f.restype = ctypes.c_int
-    for f in (L.bv_itx_bodies, L.bv_event_itx_bodies):
+    for f in (L.bv_itx_bodies, L.bv_event_itx_bodies, L.bv_event_fields_bodies):
         f.argtypes = [P, P, P]
         f.restype = ctypes.c_int
     L.bv_peer_set_hash.argtypes = [P, ctypes.c_uint32, P, P, P]

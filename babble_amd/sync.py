@@ -249,7 +249,8 @@ def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int,
     event.go:222-230).  Same results as sync_verify (tests/test_sync.py).
     fields=True: the InternalTransactions cross as fields too and ONE
     bv_verify_events_itx call verifies and folds them (no ITX JSON on the
-    host, no second call).
+    host, no second call); when an event carries BlockSignatures those cross
+    as fields as well (bv_verify_events_fields: no JSON at all).
     Falls back to sync_verify if a store hash is not a canonical Event.Hex()."""
     from .events import EventBatchBuilder
 
@@ -262,6 +263,7 @@ def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int,
         return sync_verify(wevents, repertoire_by_id, participant_event, verifier)
     eb = EventBatchBuilder()
     bsigs = []
+    bs_fields = fields and any(wevents[i].Body.BlockSignatures is not None for i in range(n))
     for i in range(n):
         we = wevents[i]
         cb, ps = pending[i]
@@ -271,9 +273,12 @@ def sync_verify_device(wevents: Sequence[WireEvent], repertoire_by_id: Dict[int,
         bsigs.append(bs)
         eb.add_event(eb.add_key(cb), we.Body.Index, we.Body.Timestamp, par, we.Body.Transactions, we.Signature,
                      itx_json=b"" if itxs is None or fields else J.slice_(itxs, lambda t: t.json()),
-                     bsig_json=b"" if bs is None else J.slice_(bs, lambda t: t.json()),
-                     itxs=itxs if fields else None)
-    res = v.verify_events_itx(eb.pack_itx()) if fields else v.verify_events(eb.pack())
+                     bsig_json=b"" if bs is None or bs_fields else J.slice_(bs, lambda t: t.json()),
+                     itxs=itxs if fields else None, bsigs=bs if bs_fields else None)
+    if bs_fields:
+        res = v.verify_events_fields(eb.pack_fields(itx_fields=True))
+    else:
+        res = v.verify_events_itx(eb.pack_itx()) if fields else v.verify_events(eb.pack())
     digests = [res.msg_hash[i].tobytes() for i in range(n)]
     itx_events = [] if fields else [i for i in range(n) if wevents[i].Body.InternalTransactions]
     itx_out = {}

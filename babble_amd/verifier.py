@@ -292,6 +292,27 @@ class Verifier:
         self._check(self._L.bv_verify_events_itx(self._ctx, ctypes.byref(cb), ctypes.byref(res), ctypes.byref(out)))
         return EventItxVerifyResult(h[:n], st[:n], bits[: (n + 63) // 64], ih[:m], ist[:m], by[:n])
 
+    def verify_events_fields(self, fb) -> "EventItxVerifyResult":
+        """bv_verify_events_fields over an events.PackedEventFieldsBatch: as
+        verify_events_itx, with the BlockSignatures built from fields too
+        (hashed into the body, not verified)."""
+        from .events import BvEventItxOut
+
+        keep: list = []
+        cb = fb.c_struct(keep)
+        n, m = fb.n_events, fb.n_itx
+        h = np.zeros((max(n, 1), 32), np.uint8)
+        st = np.zeros(max(n, 1), np.uint8)
+        bits = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        ih = np.zeros((max(m, 1), 32), np.uint8)
+        ist = np.zeros(max(m, 1), np.uint8)
+        by = np.zeros(max(n, 1), np.uint32)
+        res = native.BvResult(h.ctypes.data, st.ctypes.data, bits.ctypes.data)
+        out = BvEventItxOut(ih.ctypes.data, ist.ctypes.data, by.ctypes.data)
+        self._check(self._L.bv_verify_events_fields(self._ctx, ctypes.byref(cb), ctypes.byref(res),
+                                                    ctypes.byref(out)))
+        return EventItxVerifyResult(h[:n], st[:n], bits[: (n + 63) // 64], ih[:m], ist[:m], by[:n])
+
     def peer_set_hash(self, pubkeys: Sequence[bytes]) -> bytes:
         """bv_peer_set_hash: PeerSet.Hash over the peers' key bytes (b"" for
         an empty set, as Go's []byte{})."""
@@ -625,6 +646,23 @@ class PinnedArena:
                         itx_list_nil=None if xb.itx_list_nil is None else self.copy(xb.itx_list_nil),
                         itx_type=self.copy(xb.itx_type), itx_str_off=self.copy(xb.itx_str_off.astype(np.uint64)),
                         itx_str=self.copy(xb.itx_str))
+
+    def event_fields_batch(self, fb):
+        """The same events.PackedEventFieldsBatch with every array in pinned memory."""
+        def c(a, dt=None):
+            return None if a is None else self.copy(a if dt is None else a.astype(dt))
+
+        x = fb.ev
+        if x.itx_start is not None:
+            ev = self.event_itx_batch(x)
+        else:  # no ITX fields
+            ev = type(x)(events=self.wire(x.events), itx_start=None, itx_list_nil=c(x.itx_list_nil),
+                         itx_type=x.itx_type, itx_str_off=None, itx_str=x.itx_str)
+        return type(fb)(ev=ev,
+                        bsig_start=c(fb.bsig_start, np.uint64), bsig_list_nil=c(fb.bsig_list_nil),
+                        bsig_index=c(fb.bsig_index, np.int64), bsig_sig_off=c(fb.bsig_sig_off, np.uint64),
+                        bsig_sig=c(fb.bsig_sig), bsig_val_kind=c(fb.bsig_val_kind),
+                        bsig_val_off=c(fb.bsig_val_off, np.uint64), bsig_val_bytes=c(fb.bsig_val_bytes))
 
     def close(self):
         for p in self._blocks:

@@ -410,6 +410,58 @@ int bv_itx_bodies(const bv_event_itx_batch *batch, const uint64_t *off, uint8_t 
 int bv_event_itx_body_lens(const bv_event_itx_batch *batch, uint64_t *off /* n_events + 1 */);
 int bv_event_itx_bodies(const bv_event_itx_batch *batch, const uint64_t *off, uint8_t *out);
 
+/* A whole Event from FIELDS: bv_verify_events_itx with the seventh member of
+ * EventBody, BlockSignatures, built by the library too, so that the caller
+ * serialises no JSON at all.  Every validator ships its signature of each
+ * committed block in its next self-event (hashgraph.go:744, event.go:432-446),
+ * so most events of a SyncResponse carry one or more.  One list element is
+ *   {"Validator":V,"Index":D,"Signature":S}          (block.go:59-66)
+ * V padded StdEncoding base64 in quotes (or null), D the decimal of a Go int,
+ * S a Go string through encoding/json (Go 1.13, escapeHTML); the list is null,
+ * [] or [e,e,...] exactly as the ITX list.
+ * The block signatures are serialised and hashed ONLY: Event.Verify does not
+ * verify them (ProcessSigPool does, later, against blocks that may not exist
+ * yet; bv_verify_blocks / bv_verify_batch_text are the calls for that).
+ * result / out: exactly bv_verify_events_itx's.
+ * ev.itx_start == NULL: the batch has no ITX fields; every event's
+ * InternalTransactions is nil (null), except where ev.itx_list_nil is given
+ * and itx_list_nil[e] == 0, which is [].  No ITX array is read then.
+ * BV_E_ARGS (with a bv_last_error text): everything bv_verify_events_itx
+ * rejects except the NULL itx_start above; ev.events.bsig_off or bsig_json
+ * non-NULL; bsig_start NULL while n_events > 0, not starting at 0 or not
+ * monotone; bsig_index or bsig_sig_off NULL while n_bsig > 0; bsig_sig_off not
+ * starting at 0 or not monotone; bsig_sig NULL while bytes are named; a kind
+ * above 2; a kind BV_BSIG_VAL_BYTES with bsig_val_off NULL or not monotone
+ * (over all n_bsig + 1 offsets, the entries of other kinds included), or
+ * with bytes named and bsig_val_bytes NULL; n_bsig > 2^32.  n_bsig == 0 is
+ * valid and returns exactly what bv_verify_events_itx (for a NULL itx_start:
+ * bv_verify_events) returns for the same events with nil or "[]" fragments.
+ * Single device only: bv_group_verify_events keeps the fragments. */
+#define BV_BSIG_VAL_CREATOR 0 /* Validator = the event's creator key bytes (WireEvent.BlockSignatures) */
+#define BV_BSIG_VAL_BYTES   1 /* Validator = bsig_val_bytes[bsig_val_off[j] .. bsig_val_off[j+1]) (any length, 0 -> "") */
+#define BV_BSIG_VAL_NIL     2 /* Validator is a nil []byte -> null */
+typedef struct {
+  bv_event_itx_batch ev;        /* ev.events.bsig_off / bsig_json (and itx_off / itx_json) must be NULL */
+  const uint64_t *bsig_start;   /* n_events + 1: event e owns block signatures [bsig_start[e], bsig_start[e+1]) */
+  const uint8_t *bsig_list_nil; /* per event, 1: the slice is nil -> null (NULL: none; empty non-nil -> []) */
+  const int64_t *bsig_index;    /* per signature: BlockSignature.Index (Go int) */
+  const uint64_t *bsig_sig_off; /* n_bsig + 1 offsets into bsig_sig */
+  const uint8_t *bsig_sig;      /* BlockSignature.Signature, raw Go string bytes */
+  const uint8_t *bsig_val_kind; /* per signature (NULL: all BV_BSIG_VAL_CREATOR) */
+  const uint64_t *bsig_val_off; /* n_bsig + 1 offsets into bsig_val_bytes.  Not read when no entry is
+                                   BV_BSIG_VAL_BYTES (may be NULL).  Once any entry is, the WHOLE array must be
+                                   valid and monotone (a non-BYTES entry owns an empty range) and
+                                   bsig_val_bytes[0 .. bsig_val_off[n_bsig]) is read */
+  const uint8_t *bsig_val_bytes;
+} bv_event_fields_batch;
+
+int bv_verify_events_fields(bv_ctx *ctx, const bv_event_fields_batch *batch, bv_result *result,
+                            bv_event_itx_out *out /* may be NULL */);
+/* The serialiser's public form, as bv_event_itx_body_lens / bv_event_itx_bodies:
+ * EventBody.Marshal() of every event (host only, no device). */
+int bv_event_fields_body_lens(const bv_event_fields_batch *batch, uint64_t *off /* n_events + 1 */);
+int bv_event_fields_bodies(const bv_event_fields_batch *batch, const uint64_t *off, uint8_t *out);
+
 /* Multi-GPU: one verifier over several devices of this process (one bv_ctx
  * per device, the caller's device ordinals).  bv_group_verify_batch shards
  * the items into contiguous ranges that never split the items of one
