@@ -21,12 +21,14 @@ N = ev.N
 KW, KNWIN = 12, 11
 
 
-def chain(u2, w=KW, nwin=KNWIN):
+def chain(u2, w=KW, nwin=KNWIN, signed=True):
     """[(half, window, scalar)] of the entries k_verify_q adds for u2, in
-    order (signed w-bit windows x nwin); zero digits add nothing."""
+    order (signed w-bit windows x nwin, or K8's unsigned ones with
+    signed=False); zero digits add nothing."""
     out = []
+    digits = ev.signed_digits if signed else ev.unsigned_digits
     for h, k in enumerate(ev.glv_halves(u2)):
-        for j, d in enumerate(ev.signed_digits(abs(k), w, nwin)):
+        for j, d in enumerate(digits(abs(k), w, nwin)):
             if d:
                 out.append((h, j, (-d if k < 0 else d) * (1 << (w * j)) * (ev.LAMBDA if h else 1) % N))
     return out

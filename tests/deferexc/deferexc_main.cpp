@@ -5,7 +5,15 @@
 // tests/test_defer_exc.py builds it with the knobs at 1 and at 0 (and once
 // under AddressSanitizer + UBSan) and compares the outputs item for item.
 //
-//   deferexc batch.bin [threads]
+//   deferexc batch.bin [threads [digests.bin [8|12|18|22 [slots.txt]]]]
+//
+// digests.bin (optional; tests/test_chain_exceptions.py): n_msgs x 32 bytes
+// that REPLACE the messages' SHA-256 digests in the emulator's pipeline (the
+// oracle column still hashes the messages: ignore it then), so that the
+// valid signatures of tests/chain_vectors.py, whose digest is chosen, can be
+// replayed.  8 | 12: the per-batch key-table geometry (K8's unsigned windows
+// or K12; default 12).  18 | 22: the key cache's chain instead
+// (verify_item_gq_kc) over the sparse cached tables of slots.txt: run_cached.
 //
 // batch.bin: tests/emu/emu.py dump_batch ("BVB1").  Per item, one line:
 //   i oracle st_dev st_host redo_g redo_q redo_qf redo_gf  R_G  R_Q
@@ -115,6 +123,69 @@ int unit(const uint32_t *tab, uint32_t n_ent) {
   return n;
 }
 
+// The key cache's one-pass chain (verify_item_gq_kc<22, 6> or <18, 8>) over
+// SPARSE cached tables: each key's table is an allocation of the geometry's
+// full size, zero pages except the slots listed in `slots_path` (one line per
+// entry: <key> <slot> <x, 64 hex> <y, 64 hex>; tests/kcsmall's form), which the
+// test computes for the digits its items read.  A zero digit reads a slot that
+// is then not added.  Per item: i oracle st st 0 redo 0 0.
+fe fe_hex(const char *h) {
+  fe a;
+  for (int i = 0; i < 8; i++) {
+    char w[9] = {0};
+    memcpy(w, h + 8 * i, 8);
+    a.v[7 - i] = (uint32_t)strtoul(w, nullptr, 16);
+  }
+  return a;
+}
+
+template <int W, int NWIN>
+int run_cached_geom(const char *slots_path, const bv_batch &b, const uint8_t *kst, const uint32_t *r,
+                    const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0, int nt) {
+  constexpr uint64_t SLOTS = (uint64_t)NWIN * (1ull << (W - 1)) + 1;
+  const uint64_t n = b.n_items;
+  std::vector<uint32_t *> tabs(b.n_keys ? b.n_keys : 1, nullptr);
+  std::vector<uint64_t> addr(tabs.size(), 0);
+  for (uint32_t k = 0; k < b.n_keys; k++) {
+    tabs[k] = (uint32_t *)calloc(SLOTS * BV_ENTRY_U32, 4);  // untouched pages stay unbacked
+    if (!tabs[k]) return 2;
+    addr[k] = (uint64_t)(uintptr_t)tabs[k];
+  }
+  FILE *f = slots_path ? fopen(slots_path, "r") : nullptr;
+  if (!f) return 2;
+  unsigned key;
+  unsigned long long slot;
+  char hx[80], hy[80];
+  while (fscanf(f, "%u %llu %79s %79s", &key, &slot, hx, hy) == 4) {
+    if (key >= b.n_keys || slot >= SLOTS || strlen(hx) != 64 || strlen(hy) != 64) return 2;
+    const fe x = fe_hex(hx), y = fe_hex(hy);
+    memcpy(tabs[key] + slot * BV_ENTRY_U32, x.v, 32);
+    memcpy(tabs[key] + slot * BV_ENTRY_U32 + 8, y.v, 32);
+  }
+  fclose(f);
+  std::vector<uint8_t> s_scr;
+  uint32_t *w = aligned<uint32_t>(s_scr, n * 32 + 32);
+  const uint32_t M = 16;
+  const uint64_t T = ((n + M - 1) / M + 255) / 256 * 256;
+  parallel_for(T, nt, [&](uint64_t t) { sinv_thread(t, T, n, M, s, b.pre, w); });
+  const uint32_t *gt = emu_g_table(nt);
+  printf("unit 0\n");
+  uint64_t &cnt = bv_defer_redo_count();
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t c = cnt;
+    const uint8_t st = verify_item_gq_kc<W, NWIN>(i, b.item_key, r, s, b.pre, kst, b.item_msg, dig, w, gt, addr.data());
+    printf("%llu %d %d %d 0 %d 0 0\n", (unsigned long long)i, st0[i], st, st, cnt != c ? 1 : 0);
+  }
+  for (uint32_t *t : tabs) free(t);
+  return 0;
+}
+
+int run_cached(int kw, const char *slots_path, const bv_batch &b, const uint8_t *kst, const uint32_t *r,
+               const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0, int nt) {
+  return kw == BV_KCW ? run_cached_geom<BV_KCW, BV_KCNWIN>(slots_path, b, kst, r, s, dig, st0, nt)
+                      : run_cached_geom<BV_KC18W, BV_KC18NWIN>(slots_path, b, kst, r, s, dig, st0, nt);
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -160,9 +231,20 @@ int main(int argc, char **argv) {
   uint32_t *u12 = aligned<uint32_t>(s_u12, n * BV_U_STRIDE * 4 + 64);
   parallel_for(n_msgs, nt, [&](uint64_t m) { sha256_one(m, msg, b.msg_off, dig); });
   for (uint32_t k = 0; k < n_keys; k++) key_decode_one(k, b.key_bytes, b.key_off, kst, kxy);
+  if (argc > 3) {  // digests-in mode
+    FILE *df = fopen(argv[3], "rb");
+    if (!df) return 2;
+    const bool got = n_msgs == 0 || fread(dig, 32, n_msgs, df) == n_msgs;
+    fclose(df);
+    if (!got) return 2;
+  }
+  const int kw = argc > 4 ? atoi(argv[4]) : 12;
+  if (kw == BV_KCW || kw == BV_KC18W) return run_cached(kw, argc > 5 ? argv[5] : nullptr, b, kst, r, s, dig, st0, nt);
+  if (kw != 8 && kw != 12) return 2;
   const uint32_t *gt = emu_g_table(nt);
-  uint32_t *kt = aligned<uint32_t>(s_kt, (uint64_t)(n_keys ? n_keys : 1) * BV_K12TABLE_U32 * 4);
-  emu_build_tables(12, (uint32_t)n_keys, kxy, kst, kt, nt);
+  uint32_t *kt = aligned<uint32_t>(
+      s_kt, (uint64_t)(n_keys ? n_keys : 1) * (kw == 12 ? (uint64_t)BV_K12TABLE_U32 : (uint64_t)BV_KTABLE_U32) * 4);
+  emu_build_tables(kw, (uint32_t)n_keys, kxy, kst, kt, nt);
   uint32_t *rg = aligned<uint32_t>(s_rg, (n + 1) * RG_WORDS * 4);
   uint32_t *rq = aligned<uint32_t>(s_rq, (n + 1) * RG_WORDS * 4);
   const uint32_t M = 16;
@@ -182,10 +264,13 @@ int main(int argc, char **argv) {
     verify_item_g(i, n, b.item_key, r, s, b.pre, kst, b.item_msg, dig, w, u12, gt, rg);
     const int fg = cnt != c;
     c = cnt;
-    const uint8_t st2 = verify_item_q<BV_K12W, BV_K12NWIN>(i, n, b.item_key, r, s, b.pre, kst, u12, kt, nullptr, rg);
+    const uint8_t st2 =
+        kw == 12 ? verify_item_q<BV_K12W, BV_K12NWIN>(i, n, b.item_key, r, s, b.pre, kst, u12, kt, nullptr, rg)
+                 : verify_item_q<BV_KW, BV_KNWIN>(i, n, b.item_key, r, s, b.pre, kst, u12, kt, nullptr, rg);
     const int fq = cnt != c;
     c = cnt;
-    verify_item_qfirst<BV_K12W, BV_K12NWIN>(i, n, b.item_key, r, s, b.pre, kst, w, kt, nullptr, rq);
+    if (kw == 12) verify_item_qfirst<BV_K12W, BV_K12NWIN>(i, n, b.item_key, r, s, b.pre, kst, w, kt, nullptr, rq);
+    else verify_item_qfirst<BV_KW, BV_KNWIN>(i, n, b.item_key, r, s, b.pre, kst, w, kt, nullptr, rq);
     const int fqf = cnt != c;
     c = cnt;
     const uint8_t st6 = verify_item_gfinish(i, n, b.item_key, r, s, b.pre, kst, b.item_msg, dig, w, gt, rq);

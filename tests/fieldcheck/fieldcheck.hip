@@ -4,7 +4,10 @@
 // tests/test_gpu_field.py can compare every result with Python integers
 // (mod p and Montgomery mod N).  This checks the real ISA semantics of the
 // hand-scheduled programs (carry-outs, hazards, rare blocks), which the
-// generator's own interpreter (tests/test_field_asm.py) cannot.
+// generator's own interpreter (tests/test_field_asm.py) cannot.  Further
+// down: the zipped programs in point.h's calling patterns (k_zip) and every
+// point operation of point.h, one lane per case (k_point) — the device-only
+// bodies that the host builds (tests/emu and its kin) never compile.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../babble_amd/csrc/field.h"
@@ -258,5 +261,199 @@ extern "C" int fc_bases(int coop, uint32_t n, const uint32_t *xy, uint32_t *out,
   if (e1) (void)hipEventDestroy(e1);
   (void)hipFree(dxy);
   (void)hipFree(dout);
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+// The zipped multi-product programs of the latency point operations
+// (field_asm.h gen_zip) beyond the two of the doubling chain: ops = n x 8
+// operands (8 limbs each), out = n x 4 results.  `pat` 0 calls the program
+// with distinct registers everywhere; the others repeat, one by one, the
+// shared-input and output-on-input patterns of point.h's call sites (listed
+// in tests/test_gpu_field.py::test_zipped_point_programs_match_python_ints,
+// which computes the same products from the same operand indices).
+enum { ZP_MM = 0, ZP_MS = 1, ZP_SS = 2, ZP_MMM = 3, ZP_MMMS = 4, ZP_SSM = 5, ZP_SSS = 6, ZP_LAST = 6 };
+
+template <int PROG>
+__global__ void __launch_bounds__(256) k_zip(int pat, uint32_t n, const uint32_t *__restrict__ ops,
+                                             uint32_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fe o[8], r[4];
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[j].v[k] = ops[64 * (uint64_t)i + 8 * j + k];
+#pragma unroll
+  for (int j = 0; j < 4; j++) fe_set(r[j], 0);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (PROG == ZP_MM) {
+    if (pat == 0) fe_mul_mul_zip_asm(r[0], o[0], o[1], r[1], o[2], o[3]);
+    else if (pat == 1) fe_mul_mul_zip_asm(r[0], o[0], o[1], r[1], o[2], o[1]);  // b0 == b1
+    else if (pat == 2) {  // r0 on b0
+      r[0] = o[1];
+      fe_mul_mul_zip_asm(r[0], o[0], r[0], r[1], o[2], o[3]);
+    } else {  // r0 on b0, r1 on b1
+      r[0] = o[1], r[1] = o[3];
+      fe_mul_mul_zip_asm(r[0], o[0], r[0], r[1], o[2], r[1]);
+    }
+  } else if (PROG == ZP_MS) {
+    fe_mul_sqr_zip_asm(r[0], o[0], o[1], r[1], o[2]);
+  } else if (PROG == ZP_SS) {
+    fe_sqr_sqr_zip_asm(r[0], o[0], r[1], o[1]);
+  } else if (PROG == ZP_MMM) {
+    if (pat == 0) fe_mul_mul_mul_zip_asm(r[0], o[0], o[1], r[1], o[2], o[3], r[2], o[4], o[5]);
+    else if (pat == 1) fe_mul_mul_mul_zip_asm(r[0], o[0], o[1], r[1], o[2], o[1], r[2], o[4], o[1]);  // one b
+    else if (pat == 2) {  // r0 on b0, b1 == b2
+      r[0] = o[1];
+      fe_mul_mul_mul_zip_asm(r[0], o[0], r[0], r[1], o[2], o[3], r[2], o[4], o[3]);
+    } else {  // b0 == a2
+      fe_mul_mul_mul_zip_asm(r[0], o[0], o[1], r[1], o[2], o[3], r[2], o[1], o[5]);
+    }
+  } else if (PROG == ZP_MMMS) {
+    if (pat == 0) fe_mul_mul_mul_sqr_zip_asm(r[0], o[0], o[1], r[1], o[2], o[3], r[2], o[4], o[5], r[3], o[6]);
+    else fe_mul_mul_mul_sqr_zip_asm(r[0], o[0], o[1], r[1], o[2], o[1], r[2], o[4], o[0], r[3], o[6]);  // b0 == b1, a0 == b2
+  } else if (PROG == ZP_SSM) {
+    fe_sqr_sqr_mul_zip_asm(r[0], o[0], r[1], o[1], r[2], o[1], o[2]);  // a1 == a2 (gej_double_lat)
+  } else {
+    r[1] = o[1];
+    fe_sqr_sqr_sqr_zip_asm(r[0], o[0], r[1], r[1], r[2], o[2]);  // r1 on a1 (gej_double_lat)
+  }
+#endif
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[32 * (uint64_t)i + 8 * j + k] = r[j].v[k];
+}
+
+extern "C" int fc_zip(int prog, int pat, uint32_t n, const uint32_t *ops, uint32_t *out) {
+  static const int npat[ZP_LAST + 1] = {4, 1, 1, 4, 2, 1, 1};
+  if (prog < 0 || prog > ZP_LAST || pat < 0 || pat >= npat[prog]) return -1000;
+  uint32_t *dop = nullptr, *dr = nullptr;
+  const size_t ib = (size_t)(n ? n : 1) * 256, ob = (size_t)(n ? n : 1) * 128;
+  hipError_t e = hipMalloc(&dop, ib);
+  if (e == hipSuccess) e = hipMalloc(&dr, ob);
+  if (e == hipSuccess && n) e = hipMemcpy(dop, ops, ib, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {
+    const dim3 g((n + 255) / 256), b(256);
+    switch (prog) {
+      case ZP_MM: hipLaunchKernelGGL(k_zip<ZP_MM>, g, b, 0, 0, pat, n, dop, dr); break;
+      case ZP_MS: hipLaunchKernelGGL(k_zip<ZP_MS>, g, b, 0, 0, pat, n, dop, dr); break;
+      case ZP_SS: hipLaunchKernelGGL(k_zip<ZP_SS>, g, b, 0, 0, pat, n, dop, dr); break;
+      case ZP_MMM: hipLaunchKernelGGL(k_zip<ZP_MMM>, g, b, 0, 0, pat, n, dop, dr); break;
+      case ZP_MMMS: hipLaunchKernelGGL(k_zip<ZP_MMMS>, g, b, 0, 0, pat, n, dop, dr); break;
+      case ZP_SSM: hipLaunchKernelGGL(k_zip<ZP_SSM>, g, b, 0, 0, pat, n, dop, dr); break;
+      default: hipLaunchKernelGGL(k_zip<ZP_SSS>, g, b, 0, 0, pat, n, dop, dr); break;
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && n) e = hipMemcpy(out, dr, ob, hipMemcpyDeviceToHost);
+  (void)hipFree(dop);
+  (void)hipFree(dr);
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+// Every point operation of point.h as a unit, one lane per case: a, b and out
+// are 33 words each (four field elements and the identity flag).  XYZZ
+// operands are (X, Y, ZZ, ZZZ), Jacobian ones (X, Y, Z, -), affine ones
+// (x, y, -, -).  b's flag is the second operand's identity flag where the
+// operation takes one, and "this lane adds nothing" (take == false) for the
+// alternating-Y forms of gexz_add_ge.
+enum {
+  PO_XZ_ADD = 0, PO_XZ_ADD_LAT = 1, PO_XZ_SUM_GE_LAT = 2, PO_XZ_DOUBLE = 3,
+  PO_XZ_AFF_YALT = 4,  // gexz_add_ge_aff<false, true, true>: the throughput loops' second window
+  PO_XZ_AFF_LAT = 5,   // gexz_add_ge_aff<true>: the latency loops' second window
+  PO_XZ_AFF = 6,       // gexz_add_ge_aff<false>
+  PO_XZ_GE_XZONLY = 7, PO_XZ_GE_YALT = 8, PO_XZ_GE_YALT_XZONLY = 9,
+  PO_J_DOUBLE = 10, PO_J_DOUBLE_LAT = 11, PO_J_DOUBLE_LAT_INPLACE = 12, PO_J_ADD_GE = 13, PO_J_ADD_GE_LAT = 14,
+  PO_J_ADD = 15, PO_LAST = 15
+};
+
+template <int OP>
+__global__ void __launch_bounds__(256) k_point(uint32_t n, const uint32_t *__restrict__ a,
+                                               const uint32_t *__restrict__ b, uint32_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fe A[4], B[4];
+  const uint32_t *pa = a + 33 * (uint64_t)i, *pb = b + 33 * (uint64_t)i;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) A[j].v[k] = pa[8 * j + k], B[j].v[k] = pb[8 * j + k];
+  bool ainf = pa[32] != 0;
+  const bool bflag = pb[32] != 0;
+  if (OP >= PO_J_DOUBLE) {
+    gej R = {A[0], A[1], A[2]};
+    const gej S = {B[0], B[1], B[2]};
+    if (OP == PO_J_DOUBLE) {
+      gej D;
+      gej_double(D, R);
+      R = D;
+    } else if (OP == PO_J_DOUBLE_LAT) {
+      gej D;
+      gej_double_lat(D, R);
+      R = D;
+    } else if (OP == PO_J_DOUBLE_LAT_INPLACE) gej_double_lat(R, R);
+    else if (OP == PO_J_ADD_GE) gej_add_ge(R, ainf, B[0], B[1]);
+    else if (OP == PO_J_ADD_GE_LAT) gej_add_ge_lat(R, ainf, B[0], B[1]);
+    else gej_add(R, ainf, S, bflag);
+    A[0] = R.X, A[1] = R.Y, A[2] = R.Z;
+    fe_set(A[3], 0);
+  } else {
+    gexz R = {A[0], A[1], A[2], A[3]};
+    const gexz S = {B[0], B[1], B[2], B[3]};
+    if (OP == PO_XZ_ADD) gexz_add(R, ainf, S, bflag);
+    else if (OP == PO_XZ_ADD_LAT) gexz_add_lat(R, ainf, S, bflag);
+    else if (OP == PO_XZ_SUM_GE_LAT) {
+      gexz D = {A[0], A[1], A[2], A[3]};  // (stale where the result is the identity)
+      bool dinf;
+      gexz_sum_ge_lat(D, dinf, A[0], A[1], ainf, B[0], B[1], bflag);
+      R = D, ainf = dinf;
+    } else if (OP == PO_XZ_DOUBLE) {
+      gexz D;
+      gexz_double(D, R);
+      R = D;
+    } else if (OP == PO_XZ_AFF_YALT) gexz_add_ge_aff<false, true, true>(R, ainf, B[0], B[1]);
+    else if (OP == PO_XZ_AFF_LAT) gexz_add_ge_aff<true>(R, ainf, B[0], B[1]);
+    else if (OP == PO_XZ_AFF) gexz_add_ge_aff<false>(R, ainf, B[0], B[1]);
+    else if (OP == PO_XZ_GE_XZONLY) gexz_add_ge(R, ainf, B[0], B[1], true);
+    else if (OP == PO_XZ_GE_YALT) gexz_add_ge<true, true>(R, ainf, B[0], B[1], false, false, !bflag);
+    else gexz_add_ge<true, true>(R, ainf, B[0], B[1], true, false, !bflag);
+    A[0] = R.X, A[1] = R.Y, A[2] = R.ZZ, A[3] = R.ZZZ;
+  }
+  uint32_t *o = out + 33 * (uint64_t)i;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[8 * j + k] = A[j].v[k];
+  o[32] = ainf ? 1u : 0u;
+}
+
+extern "C" int fc_point(int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+  if (op < 0 || op > PO_LAST) return -1000;
+  uint32_t *da = nullptr, *db = nullptr, *dr = nullptr;
+  const size_t bytes = (size_t)(n ? n : 1) * 33 * 4;
+  hipError_t e = hipMalloc(&da, bytes);
+  if (e == hipSuccess) e = hipMalloc(&db, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dr, bytes);
+  if (e == hipSuccess && n) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {
+    const dim3 g((n + 255) / 256), t(256);
+#define FC_POINT_CASE(OP) \
+  case OP: hipLaunchKernelGGL(k_point<OP>, g, t, 0, 0, n, da, db, dr); break;
+    switch (op) {
+      FC_POINT_CASE(0) FC_POINT_CASE(1) FC_POINT_CASE(2) FC_POINT_CASE(3) FC_POINT_CASE(4) FC_POINT_CASE(5)
+      FC_POINT_CASE(6) FC_POINT_CASE(7) FC_POINT_CASE(8) FC_POINT_CASE(9) FC_POINT_CASE(10) FC_POINT_CASE(11)
+      FC_POINT_CASE(12) FC_POINT_CASE(13) FC_POINT_CASE(14) FC_POINT_CASE(15)
+    }
+#undef FC_POINT_CASE
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && n) e = hipMemcpy(out, dr, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(da);
+  (void)hipFree(db);
+  (void)hipFree(dr);
   return e == hipSuccess ? 0 : -(int)e;
 }

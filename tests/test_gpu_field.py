@@ -4,7 +4,10 @@ checked against Python integers: fe_mul / fe_sqr / fe_add / fe_sub mod p
 (weakly reduced: < 2^256 and congruent), sc_mont (a b 2^-256 mod N, < N) and
 fe_inv_var.  Operands include limb patterns that drive every rare block of
 the programs (fold carry-outs, tails), so the hardware's carry / hazard
-behaviour is exercised, not just the generator's interpreter."""
+behaviour is exercised, not just the generator's interpreter.  Also every
+zipped multi-product program in the calling patterns point.h uses (shared
+inputs, outputs on inputs) and every point operation of point.h as a unit:
+the bodies under __HIP_DEVICE_COMPILE__ that no host build compiles."""
 import ctypes
 import os
 import random
@@ -379,3 +382,269 @@ def test_coop_base_chain_equals_per_lane(w, nwin):
     zi = pow(Z, -1, P)
     assert (X * zi * zi % P, Y * zi * zi * zi % P) == _ec_mul(2 ** (w * (nwin - 1)), pts[0])
     print(f"\nbase chain {w}x{nwin - 1} doublings, {len(pts)} keys: per-lane {ms[0]:.3f} ms, coop {ms[1]:.3f} ms")
+
+
+def _pack_fast(xs):
+    return np.frombuffer(b"".join(x.to_bytes(32, "little") for x in xs), dtype="<u4").reshape(len(xs), 8).copy()
+
+
+def _rot(x, k):
+    """x's eight 32-bit limbs rotated up by k places."""
+    k *= 32
+    return ((x << k) | (x >> (256 - k))) & (2**256 - 1)
+
+
+# (result -> (operand, operand)) of every program and calling pattern of fc_zip
+_ZIP = {
+    "mul_mul": (0, [[(0, 1), (2, 3)], [(0, 1), (2, 1)], [(0, 1), (2, 3)], [(0, 1), (2, 3)]]),
+    "mul_sqr": (1, [[(0, 1), (2, 2)]]),
+    "sqr_sqr": (2, [[(0, 0), (1, 1)]]),
+    "mul_mul_mul": (3, [[(0, 1), (2, 3), (4, 5)], [(0, 1), (2, 1), (4, 1)], [(0, 1), (2, 3), (4, 3)],
+                        [(0, 1), (2, 3), (1, 5)]]),
+    "mul_mul_mul_sqr": (4, [[(0, 1), (2, 3), (4, 5), (6, 6)], [(0, 1), (2, 1), (4, 0), (6, 6)]]),
+    "sqr_sqr_mul": (5, [[(0, 0), (1, 1), (1, 2)]]),
+    "sqr_sqr_sqr": (6, [[(0, 0), (1, 1), (2, 2)]]),
+}
+_ZIP_OPS = {}
+
+
+def _zip_operands():
+    """Eight operands a lane: (a, b) of _pairs() and of the near-2^256 values
+    of test_zipped_programs_match_python_ints, and six more by fixed maps
+    that keep an all-ones-heavy value all-ones-heavy (limb rotations, and the
+    complement of an xor), so every component of a program sees a
+    rare-block operand in the same lane."""
+    if not _ZIP_OPS:
+        a, b = _pairs(3000, 41)
+        rng = random.Random(43)
+        for _ in range(1500):
+            a.append(2**256 - 1 - rng.getrandbits(rng.choice([1, 4, 12, 33, 70])))
+            b.append(2**256 - 1 - rng.getrandbits(rng.choice([1, 4, 12, 33, 70])))
+        a = [x % 2**256 for x in a]
+        b = [x % 2**256 for x in b]
+        full = 2**256 - 1
+        cols = [a, b, [_rot(x, 1) for x in a], [_rot(y, 2) for y in b],
+                [full ^ _rot(x, 3) ^ _rot(y, 6) for x, y in zip(a, b)], [_rot(y, 5) for y in b],
+                [full ^ x ^ y for x, y in zip(a, b)], [0] * len(a)]
+        _ZIP_OPS["cols"] = cols
+        _ZIP_OPS["packed"] = np.ascontiguousarray(np.stack([_pack_fast(c) for c in cols], axis=1))
+    return _ZIP_OPS["cols"], _ZIP_OPS["packed"]
+
+
+@pytest.mark.parametrize("prog", sorted(_ZIP))
+def test_zipped_point_programs_match_python_ints(prog):
+    """Every component of the zipped programs the latency point operations
+    are built on (fe_mul_mul / fe_mul_sqr / fe_sqr_sqr / fe_mul_mul_mul /
+    fe_mul_mul_mul_sqr _zip_asm; the doubling chain's two programs once more
+    in their call-site form), < 2^256 and congruent mod p.  Pattern 0 calls a
+    program with distinct registers; the others are point.h's call sites:
+      fe_mul_mul:  1 b0 == b1          gej_add_ge_lat (x2 Z1Z1, Z1 Z1Z1), gexz_sum_ge_lat / gexz_add_ge_aff (P PP, x1 PP)
+                   2 r0 on b0          gexz_sum_ge_lat (t, R, t, u, y1, PPP)
+                   3 r0 on b0, r1 on b1  gej_add_ge_lat (t, R, t, HHH, r.Y, HHH)
+      fe_mul_mul_mul:  1 b0 == b1 == b2   gexz_add_ge_lat / gexz_add_lat (P PP, X PP, ZZ PP)
+                   2 r0 on b0, b1 == b2   gexz_add_ge_lat / gexz_add_lat (t, R, t, u, S1, PPP, ., W12, PPP)
+                   3 b0 == a2          gexz_add_lat (S2, b.Y, r.ZZZ, Z12, r.ZZ, b.ZZ, W12, r.ZZZ, b.ZZZ)
+      fe_mul_mul_mul_sqr:  1 b0 == b1, a0 == b2   gej_add_ge_lat (H HH, X HH, Z H, R^2)
+      fe_sqr_sqr_mul:  a1 == a2        gej_double_lat (X^2, Y^2, Y Z)
+      fe_sqr_sqr_sqr:  r1 on a1        gej_double_lat (C, B, t, t, F, E)
+    fe_mul_sqr and fe_sqr_sqr have one call form (distinct registers)."""
+    code, pats = _ZIP[prog]
+    cols, packed = _zip_operands()
+    n = len(cols[0])
+    L = _lib()
+    L.fc_zip.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    L.fc_zip.restype = ctypes.c_int
+    for pat, comps in enumerate(pats):
+        out = np.zeros((n, 4, 8), np.uint32)
+        assert L.fc_zip(code, pat, n, packed.ctypes.data, out.ctypes.data) == 0
+        for k, (ia, ib) in enumerate(comps):
+            r = _unpack(out[:, k, :])
+            bad = [(i, hex(cols[ia][i]), hex(cols[ib][i]), hex(z)) for i, z in enumerate(r)
+                   if z >= 2**256 or (z - cols[ia][i] * cols[ib][i]) % P]
+            assert not bad, (prog, pat, k, len(bad), bad[:3])
+
+
+GX = 0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798
+GY = 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8
+_POOL = []
+
+
+def _pool():
+    """Points the cases draw from: G, 2 G, (N - 1) G (extreme coordinates)
+    and an arithmetic progression from a random point (one addition each)."""
+    if not _POOL:
+        G = (GX, GY)
+        rng = random.Random(53)
+        _POOL.extend([G, _ec_mul(2, G), _ec_mul(N - 1, G)])
+        pt, step = _ec_mul(rng.randrange(1, N), G), _ec_mul(rng.randrange(1, N), G)
+        for _ in range(253):
+            _POOL.append(pt)
+            pt = _ec_add(pt, step)
+    return _POOL
+
+
+def _neg(pt):
+    return None if pt is None else (pt[0], (P - pt[1]) % P)
+
+
+Z_CLASSES = ("one", "p-1", "small", "random")
+
+
+def _zs(rng, cls):
+    """Z = 1, p - 1, small (its ZZ and ZZZ can also be given as v + p) or random."""
+    return [1, P - 1, rng.randrange(2, 2**10), rng.randrange(1, P)][cls]
+
+
+def _lift(v, on):
+    """v, or with `on` the non-canonical v + p where that is weakly reduced (< 2^256)."""
+    return v + P if on and v + P < 2**256 else v
+
+
+def _xyzz(pt, z, nc):
+    if pt is None:
+        return [0, 0, 0, 0, 1]
+    zz, zzz = z * z % P, z * z * z % P
+    return [_lift(pt[0] * zz % P, nc), _lift(pt[1] * zzz % P, nc), _lift(zz, nc), _lift(zzz, nc), 0]
+
+
+def _jac(pt, z, nc):
+    if pt is None:
+        return [0, 0, 0, 0, 1]
+    return [_lift(pt[0] * z * z % P, nc), _lift(pt[1] * z * z * z % P, nc), _lift(z, nc), 0, 0]
+
+
+def _aff(pt, z=None, nc=0):
+    return [0, 0, 0, 0, 1] if pt is None else [pt[0], pt[1], 1, 1, 0]
+
+
+# op -> (code, first operand's form, second operand's form, result's form, kinds, expected)
+# kinds: 0 generic, 1 P + P, 2 P + (-P), 3 identity + P, 4 P + identity, 5 identity + identity
+_POINT_OPS = {
+    "gexz_add": (0, _xyzz, _xyzz, "xyzz", (0, 1, 2, 3, 4, 5)),
+    "gexz_add_lat": (1, _xyzz, _xyzz, "xyzz", (0, 1, 2, 3, 4, 5)),
+    "gexz_sum_ge_lat": (2, _aff, _aff, "xyzz", (0, 1, 2, 3, 4, 5)),
+    "gexz_double": (3, _xyzz, _aff, "xyzz", (1,)),
+    "gexz_add_ge_aff<throughput,YALT>": (4, _aff, _aff, "xyzz-neg", (0, 1, 2)),
+    "gexz_add_ge_aff<LAT>": (5, _aff, _aff, "xyzz", (0, 1, 2)),
+    "gexz_add_ge_aff<throughput>": (6, _aff, _aff, "xyzz", (0, 1, 2)),
+    "gexz_add_ge(xz_only)": (7, _xyzz, _aff, "xz", (0, 1, 2, 3)),
+    "gexz_add_ge<YALT>": (8, _xyzz, _aff, "xyzz-neg", (0, 1, 2, 3, 4, 5)),
+    "gexz_add_ge<YALT>(xz_only)": (9, _xyzz, _aff, "xz", (0, 1, 2, 3, 4, 5)),
+    "gej_double": (10, _jac, _aff, "jac", (1,)),
+    "gej_double_lat": (11, _jac, _aff, "jac", (1,)),
+    "gej_double_lat(in place)": (12, _jac, _aff, "jac", (1,)),
+    "gej_add_ge": (13, _jac, _aff, "jac", (0, 1, 2, 3)),
+    "gej_add_ge_lat": (14, _jac, _aff, "jac", (0, 1, 2, 3)),
+    "gej_add": (15, _jac, _jac, "jac", (0, 1, 2, 3, 4, 5)),
+}
+POINT_LANES = 768
+
+
+@pytest.mark.parametrize("op", list(_POINT_OPS))
+def test_point_ops_match_python_ints(op):
+    """Every point operation of point.h as a unit on the device (the
+    __HIP_DEVICE_COMPILE__ bodies no host build compiles), 768 lanes each,
+    compared as affine points with _ec_add: generic sums, P + P with the two
+    operands in different projective representations (the doubling branch),
+    P + (-P) (the identity), and the identity on either side and on both
+    sides where the operation takes it.  Operands: G, 2 G and (N - 1) G in
+    the first lanes of every kind; Z = 1, p - 1, small and random on each
+    projective operand of every kind, in every pairing of the two operands'
+    classes (asserted below: the kind and the classes are chosen by
+    independent indices); and, for small Z, every
+    coordinate that allows it given as v + p — a legal weakly reduced input
+    with which fe_is_zero has to see p as well as 0 for the P + P and
+    P + (-P) branches to be taken.  XYZZ results must keep ZZ^3 == ZZZ^2;
+    the identity flag is compared exactly.
+
+    The alternating-Y forms (YALT, the default build's throughput loops)
+    return the OPPOSITE of the sum; a lane that adds nothing (the second
+    operand's flag: take == false) negates its point, and an accumulator at
+    the identity copies the entry it is handed (the caller pre-negates it).
+    With xz_only only X and ZZ of a common-path sum are defined: x alone is
+    compared there.  gexz_add_ge_aff is run in the three instantiations a
+    default build has: <false, true, true> and <true> from the kernels'
+    second window, and the plain <false>."""
+    code, fa, fb, form, kinds = _POINT_OPS[op]
+    yalt = "YALT" in op and "aff" not in op
+    pool = _pool()
+    rng = random.Random(1000 + code)
+    A, B, want = [], [], []
+    seen = set()
+    for i in range(POINT_LANES):
+        # the case kind cycles fastest; the Z classes of the two operands, the non-canonical form and the
+        # extreme points are functions of q alone, so every kind meets every one of them
+        kind, q = kinds[i % len(kinds)], i // len(kinds)
+        ca, cb, lift = q % 4, (q // 4) % 4, (q // 16) % 2
+        a = pool[q % 3] if q < 48 else rng.choice(pool)
+        b = a if kind == 1 else (_neg(a) if kind == 2 else rng.choice(pool))
+        seen.add((kind, "pt", q % 3 if q < 48 else 3))
+        if kind in (3, 5):
+            a = None
+        if kind in (4, 5):
+            b = None
+        if a is not None and fa is not _aff:
+            seen.add((kind, "za", ca, lift))
+        if b is not None and fb is not _aff:
+            seen.add((kind, "zb", cb, lift))
+        if a is not None and b is not None and fa is not _aff and fb is not _aff:
+            seen.add((kind, "zab", ca, cb))
+        za, zb = _zs(rng, ca), _zs(rng, cb)
+        A.append(fa(a, za, lift))
+        if yalt:  # the second operand's flag is "adds nothing"; the entry itself is always a point
+            e = b if b is not None else rng.choice(pool)
+            B.append(fb(e, zb, lift)[:4] + [1 if b is None else 0])
+            want.append(e if a is None and b is not None else _neg(_ec_add(a, b)))
+        else:
+            B.append(fb(b, zb, lift))
+            w = _ec_add(a, b)
+            want.append(_neg(w) if form == "xyzz-neg" else w)
+    assert sum(w is None for w in want) >= POINT_LANES // 12 or kinds == (1,)
+    # every kind has seen G, 2 G, (N - 1) G and pool points, and every Z class (plain and v + p) on each
+    # projective operand it has, in every pairing of the two operands' classes
+    both = [(c, d) for c in range(4) for d in range(4)]
+    for kind in kinds:
+        got = {t[1:] for t in seen if t[0] == kind}
+        assert {("pt", x) for x in range(4)} <= got, (op, kind)
+        if fa is not _aff and kind not in (3, 5):
+            assert {("za", c, l) for c, l in both if l < 2} <= got, (op, kind)
+        if fb is not _aff and kind not in (4, 5):
+            assert {("zb", c, l) for c, l in both if l < 2} <= got, (op, kind)
+        if fa is not _aff and fb is not _aff and kind in (0, 1, 2):
+            assert {("zab", c, d) for c, d in both} <= got, (op, kind)
+
+    def words(rows):
+        m = np.zeros((len(rows), 33), np.uint32)
+        for j in range(4):
+            m[:, 8 * j:8 * j + 8] = _pack_fast([r[j] for r in rows])
+        m[:, 32] = [r[4] for r in rows]
+        return m
+
+    MA, MB = words(A), words(B)
+    R = np.zeros_like(MA)
+    L = _lib()
+    L.fc_point.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.fc_point.restype = ctypes.c_int
+    assert L.fc_point(code, len(A), MA.ctypes.data, MB.ctypes.data, R.ctypes.data) == 0
+    cols = [_unpack(R[:, 8 * j:8 * j + 8]) for j in range(4)]
+    for i, w in enumerate(want):
+        what = (op, i, kinds[i % len(kinds)])
+        raw = [cols[j][i] for j in range(4)]
+        assert all(v < 2**256 for v in raw), what
+        X, Y, Z2, Z3 = (v % P for v in raw)
+        if w is None:
+            assert R[i, 32] == 1, (what, "expected the identity")
+            continue
+        assert R[i, 32] == 0, what
+        if form == "jac":
+            assert Z2, what
+            zi = pow(Z2, -1, P)
+            got = (X * zi * zi % P, Y * zi * zi * zi % P)
+        elif form == "xz":
+            assert Z2, what
+            assert X * pow(Z2, -1, P) % P == w[0], what
+            continue
+        else:
+            assert Z2 and pow(Z2, 3, P) == pow(Z3, 2, P), what
+            got = (X * pow(Z2, -1, P) % P, Y * pow(Z3, -1, P) % P)
+        assert got == w, what
