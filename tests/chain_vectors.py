@@ -27,6 +27,11 @@ acc == +-s mod N, exact):
     for u1.
   * generic path (verify_item_generic): u2 Q whole, then the generator's
     26-bit signed windows ascending.  u2 c + A_G = +-B_G is solved for c.
+  * host-entry order, every key-table geometry (k_verify_qf, then
+    k_verify_gf: bv_item_pipe, which bv_verify_batch, bv_verify_batch_text,
+    bv_verify_events* and bv_verify_blocks run): the key chain from the
+    identity, half 0 then half 1, then the generator's windows onto R_Q
+    (host_steps).  The same equation, solved for u2 with c fixed.
   * k_small without a key table (cold): wave 3 adds the G sum in phase
     kColdGJoin and +-phi(2^i Q) for the NAF digits of k2 ascending, at most
     kColdBudget additions a phase from the entries published so far
@@ -49,7 +54,10 @@ not modelled, nor targeted), as is each key chain's u1 G; wave 1's k1 chain
 on the cold path, the generator tree and the warm tree's leaf pairs are
 modelled (so a collision there would be reported) but never targeted: their
 operands differ in magnitude by construction.  The host-record form of
-k_small (rec != NULL) is out of scope.
+k_small (rec != NULL) runs the same two schedules over the u1, k1, k2 that
+bv_host_item_records forms, so the cold and warm vectors serve it as they are.
+In the host-entry order the key chain is modelled window by window and the
+generator chain likewise; only the generator windows are targeted.
 """
 import os
 import random
@@ -126,6 +134,15 @@ def generic_steps(u1, u2, c):
         if d:
             out.append((("g", j), (d << (GW * j)) % N))
     return out
+
+
+def host_steps(u1, u2, c, geom):
+    """The host-entry order (k_verify_qf, then k_verify_gf): the key chain of
+    `geom` from the identity, half 0 then half 1, windows ascending, then
+    u1's signed 26-bit generator windows ascending onto R_Q (generic_steps'
+    generator steps)."""
+    w, nwin, signed = K_GEOMETRIES[geom]
+    return [(("k", h, j), x * c % N) for h, j, x in dv.chain(u2, w, nwin, signed)] + generic_steps(u1, u2, c)[1:]
 
 
 def collisions(steps):
@@ -214,6 +231,67 @@ def generic_vectors():
                 tag = f"generic/{rep}/g{g[at][0][1]}/{'dbl' if sign > 0 else 'inv'}"
                 out.append(Vec(tag, c, u1, u2, rs[0], rs[1], g[at][0], sign))
     _CACHE["generic"] = out
+    return out
+
+
+def host_vectors():
+    """The host-entry order, on k_vectors' two keys: R_Q = u2 Q, whole when
+    k_verify_gf adds the generator windows onto it, meets the first, a middle
+    and the last non-zero generator window of u1 as a doubling and as
+    P + (-P): 12 vectors (the 2 that meet the last window's opposite end on
+    the identity: REJECT).  u1 is drawn and the collision solved for u2 with
+    c fixed, u2 = (+-g_at - sum of the windows below) / c, so every key-table
+    geometry runs the same vectors on two key tables; that u2's own key chain
+    (from the identity) meets nothing under a geometry is what
+    tests/test_chain_exceptions.py checks with host_steps."""
+    if "host" in _CACHE:
+        return _CACHE["host"]
+    rng = random.Random(0x4057)
+    out = []
+    for kidx in range(2):
+        c = random.Random(0xC0 + kidx).randrange(1, N)
+        for which in range(3):
+            for sign in (1, -1):
+                while True:
+                    u1 = rng.randrange(1, N)
+                    g = generic_steps(u1, 0, 1)[1:]
+                    if len(g) < 3:
+                        continue
+                    at = _targets(g)[which]
+                    a = sum(x for _, x in g[:at]) % N
+                    u2 = (sign * g[at][1] - a) * pow(c, -1, N) % N
+                    rs = sign_for(c, u1, u2) if u2 else None
+                    if rs:
+                        break
+                tag = f"host/k{kidx}/g{g[at][0][1]}/{'dbl' if sign > 0 else 'inv'}"
+                out.append(Vec(tag, c, u1, u2, rs[0], rs[1], g[at][0], sign))
+    _CACHE["host"] = out
+    return out
+
+
+def host_invalid_twins():
+    """host_vectors' chains under signatures that do NOT verify: the same c,
+    u1 and u2, so the same additions and the same collision, with another s'
+    (drawn), r' = u2 s' and the digest u1 s' — r' is then not x(R), and the
+    status is REJECT.  What they are for: an unchecked chain (BV_DEFER_EXC)
+    that has met P == 0 ends, one addition later, on X = ZZ = 0, which
+    final_check's X == r ZZ takes for ANY r; an item that is flagged and not
+    redone therefore ACCEPTs, which a valid signature cannot show.  12."""
+    if "host-twins" in _CACHE:
+        return _CACHE["host-twins"]
+    rng = random.Random(0x7714)
+    out = []
+    for v in host_vectors():
+        x_r = gs.scalar_mult(v.total, gs.G)[0] % N if v.total else None
+        while True:
+            s = rng.randrange(1, (N - 1) // 2 + 1)
+            r = v.u2 * s % N
+            if r and r != x_r and s != v.s:
+                break
+        t = Vec(v.tag.replace("host/", "host-invalid/"), v.c, v.u1, v.u2, r, s, v.target, v.sign)
+        t.want = gs.REJECT
+        out.append(t)
+    _CACHE["host-twins"] = out
     return out
 
 

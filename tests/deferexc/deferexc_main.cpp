@@ -5,7 +5,7 @@
 // tests/test_defer_exc.py builds it with the knobs at 1 and at 0 (and once
 // under AddressSanitizer + UBSan) and compares the outputs item for item.
 //
-//   deferexc batch.bin [threads [digests.bin [8|12|18|22 [slots.txt]]]]
+//   deferexc batch.bin [threads [digests.bin [8|12|18|22 [slots.txt|- [gslots.txt]]]]]
 //
 // digests.bin (optional; tests/test_chain_exceptions.py): n_msgs x 32 bytes
 // that REPLACE the messages' SHA-256 digests in the emulator's pipeline (the
@@ -13,7 +13,13 @@
 // valid signatures of tests/chain_vectors.py, whose digest is chosen, can be
 // replayed.  8 | 12: the per-batch key-table geometry (K8's unsigned windows
 // or K12; default 12).  18 | 22: the key cache's chain instead
-// (verify_item_gq_kc) over the sparse cached tables of slots.txt: run_cached.
+// (verify_item_gq_kc) over the sparse cached tables of slots.txt: run_cached,
+// which also runs the host entries' order over them (verify_item_qfirst<W>,
+// verify_item_gfinish) and fills st_host, redo_qf and redo_gf.  gslots.txt: the
+// generator table is a sparse one too (sparse_g_table) instead of the
+// emulator's, for a build with the product's generator geometry, whose full
+// table no host holds (slots.txt is "-" for 8 | 12, which build their own key
+// tables).
 //
 // batch.bin: tests/emu/emu.py dump_batch ("BVB1").  Per item, one line:
 //   i oracle st_dev st_host redo_g redo_q redo_qf redo_gf  R_G  R_Q
@@ -25,6 +31,8 @@
 // affine forms) on accumulators equal to +-the entry (ZZ3 must be 0 mod p)
 // and on other entries (ZZ3 != 0, the same group element as the checked
 // form); any failure exits 1.
+#include <sys/mman.h>
+
 #include <cstdio>
 
 #include "../emu/emu.cpp"
@@ -128,7 +136,7 @@ int unit(const uint32_t *tab, uint32_t n_ent) {
 // full size, zero pages except the slots listed in `slots_path` (one line per
 // entry: <key> <slot> <x, 64 hex> <y, 64 hex>; tests/kcsmall's form), which the
 // test computes for the digits its items read.  A zero digit reads a slot that
-// is then not added.  Per item: i oracle st st 0 redo 0 0.
+// is then not added.  Per item: i oracle st st_host 0 redo redo_qf redo_gf.
 fe fe_hex(const char *h) {
   fe a;
   for (int i = 0; i < 8; i++) {
@@ -139,9 +147,33 @@ fe fe_hex(const char *h) {
   return a;
 }
 
+// The GENERATOR table of the geometry this program was built with, SPARSE in
+// the same way (a build with the product's 26 x 10 windows: 21.5 GB of address
+// space, no page touched except the listed slots): one line per entry,
+// <slot> <x, 64 hex> <y, 64 hex>, slot j 2^(BV_GW-1) + |d| holding
+// |d| 2^(BV_GW j) G, which the test computes for the digits of its items' u1.
+const uint32_t *sparse_g_table(const char *path) {
+  const size_t bytes = BV_GTABLE_U32 * 4 + 64;
+  void *p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+  FILE *f = fopen(path, "r");
+  if (p == MAP_FAILED || !f) return nullptr;
+  uint32_t *tab = (uint32_t *)p;
+  unsigned long long slot;
+  char hx[80], hy[80];
+  while (fscanf(f, "%llu %79s %79s", &slot, hx, hy) == 3) {
+    if (slot > (uint64_t)BV_GNWIN * BV_GENT || strlen(hx) != 64 || strlen(hy) != 64) return nullptr;
+    const fe x = fe_hex(hx), y = fe_hex(hy);
+    memcpy(tab + slot * BV_ENTRY_U32, x.v, 32);
+    memcpy(tab + slot * BV_ENTRY_U32 + 8, y.v, 32);
+  }
+  fclose(f);
+  return tab;
+}
+
 template <int W, int NWIN>
-int run_cached_geom(const char *slots_path, const bv_batch &b, const uint8_t *kst, const uint32_t *r,
-                    const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0, int nt) {
+int run_cached_geom(const char *slots_path, const uint32_t *gt, const bv_batch &b, const uint8_t *kst,
+                    const uint32_t *r, const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0,
+                    int nt) {
   constexpr uint64_t SLOTS = (uint64_t)NWIN * (1ull << (W - 1)) + 1;
   const uint64_t n = b.n_items;
   std::vector<uint32_t *> tabs(b.n_keys ? b.n_keys : 1, nullptr);
@@ -168,22 +200,32 @@ int run_cached_geom(const char *slots_path, const bv_batch &b, const uint8_t *ks
   const uint32_t M = 16;
   const uint64_t T = ((n + M - 1) / M + 255) / 256 * 256;
   parallel_for(T, nt, [&](uint64_t t) { sinv_thread(t, T, n, M, s, b.pre, w); });
-  const uint32_t *gt = emu_g_table(nt);
+  if (!gt) gt = emu_g_table(nt);
+  std::vector<uint8_t> s_rq;
+  uint32_t *rq = aligned<uint32_t>(s_rq, (n + 1) * RG_WORDS * 4);
   printf("unit 0\n");
   uint64_t &cnt = bv_defer_redo_count();
   for (uint64_t i = 0; i < n; i++) {
-    const uint64_t c = cnt;
+    uint64_t c = cnt;
     const uint8_t st = verify_item_gq_kc<W, NWIN>(i, b.item_key, r, s, b.pre, kst, b.item_msg, dig, w, gt, addr.data());
-    printf("%llu %d %d %d 0 %d 0 0\n", (unsigned long long)i, st0[i], st, st, cnt != c ? 1 : 0);
+    const int fq = cnt != c;
+    // the host entries' order over the same tables (k_verify_qf<W>, k_verify_gf)
+    c = cnt;
+    verify_item_qfirst<W, NWIN>(i, n, b.item_key, r, s, b.pre, kst, w, nullptr, addr.data(), rq);
+    const int fqf = cnt != c;
+    c = cnt;
+    const uint8_t st6 = verify_item_gfinish(i, n, b.item_key, r, s, b.pre, kst, b.item_msg, dig, w, gt, rq);
+    const int fgf = cnt != c;
+    printf("%llu %d %d %d 0 %d %d %d\n", (unsigned long long)i, st0[i], st, st6, fq, fqf, fgf);
   }
   for (uint32_t *t : tabs) free(t);
   return 0;
 }
 
-int run_cached(int kw, const char *slots_path, const bv_batch &b, const uint8_t *kst, const uint32_t *r,
-               const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0, int nt) {
-  return kw == BV_KCW ? run_cached_geom<BV_KCW, BV_KCNWIN>(slots_path, b, kst, r, s, dig, st0, nt)
-                      : run_cached_geom<BV_KC18W, BV_KC18NWIN>(slots_path, b, kst, r, s, dig, st0, nt);
+int run_cached(int kw, const char *slots_path, const uint32_t *gt, const bv_batch &b, const uint8_t *kst,
+               const uint32_t *r, const uint32_t *s, const uint32_t *dig, const std::vector<uint8_t> &st0, int nt) {
+  return kw == BV_KCW ? run_cached_geom<BV_KCW, BV_KCNWIN>(slots_path, gt, b, kst, r, s, dig, st0, nt)
+                      : run_cached_geom<BV_KC18W, BV_KC18NWIN>(slots_path, gt, b, kst, r, s, dig, st0, nt);
 }
 
 }  // namespace
@@ -239,9 +281,12 @@ int main(int argc, char **argv) {
     if (!got) return 2;
   }
   const int kw = argc > 4 ? atoi(argv[4]) : 12;
-  if (kw == BV_KCW || kw == BV_KC18W) return run_cached(kw, argc > 5 ? argv[5] : nullptr, b, kst, r, s, dig, st0, nt);
+  const uint32_t *gt = argc > 6 ? sparse_g_table(argv[6]) : nullptr;
+  if (argc > 6 && !gt) return 2;
+  if (kw == BV_KCW || kw == BV_KC18W)
+    return run_cached(kw, argc > 5 ? argv[5] : nullptr, gt, b, kst, r, s, dig, st0, nt);
   if (kw != 8 && kw != 12) return 2;
-  const uint32_t *gt = emu_g_table(nt);
+  if (!gt) gt = emu_g_table(nt);
   uint32_t *kt = aligned<uint32_t>(
       s_kt, (uint64_t)(n_keys ? n_keys : 1) * (kw == 12 ? (uint64_t)BV_K12TABLE_U32 : (uint64_t)BV_KTABLE_U32) * 4);
   emu_build_tables(kw, (uint32_t)n_keys, kxy, kst, kt, nt);
