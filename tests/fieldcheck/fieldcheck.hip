@@ -7,7 +7,9 @@
 // generator's own interpreter (tests/test_field_asm.py) cannot.  Further
 // down: the zipped programs in point.h's calling patterns (k_zip) and every
 // point operation of point.h, one lane per case (k_point) — the device-only
-// bodies that the host builds (tests/emu and its kin) never compile.
+// bodies that the host builds (tests/emu and its kin) never compile.  Last:
+// item_scalars (k_scalars), the digest and r of an item to u1 and the GLV
+// halves of u2.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../babble_amd/csrc/field.h"
@@ -455,5 +457,58 @@ extern "C" int fc_point(int op, uint32_t n, const uint32_t *a, const uint32_t *b
   (void)hipFree(da);
   (void)hipFree(db);
   (void)hipFree(dr);
+  return e == hipSuccess ? 0 : -(int)e;
+}
+
+// verify_core.h's item_scalars as it stands, one item per lane: u1 = e s^-1
+// mod N from the UNREDUCED 256-bit digest e, and the GLV split of
+// u2 = r s^-1.  dig and r_be: 8 words per item, the 32 big-endian bytes as the
+// kernels read them (sc_load_be_words); w: s^-1 2^256 mod N in 8 limbs, what
+// k_sinv leaves; item i reads digest i.  out: 17 words per item, u1[8],
+// k1[4], k2[4] and the sign word.
+__global__ void __launch_bounds__(256) k_scalars(uint32_t n, const uint32_t *__restrict__ dig,
+                                                 const uint32_t *__restrict__ r_be,
+                                                 const uint32_t *__restrict__ w,
+                                                 const uint32_t *__restrict__ item_msg, uint32_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t u1[8], k1[4], k2[4], signs;
+  item_scalars(i, r_be, item_msg, dig, w, u1, k1, k2, signs);
+  uint32_t *o = out + 17 * (uint64_t)i;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o[k] = u1[k];
+#pragma unroll
+  for (int k = 0; k < 4; k++) o[8 + k] = k1[k], o[12 + k] = k2[k];
+  o[16] = signs;
+}
+
+extern "C" int fc_scalars(uint32_t n, const uint32_t *dig, const uint32_t *r_be, const uint32_t *w, uint32_t *out) {
+  uint32_t *dd = nullptr, *dr = nullptr, *dw = nullptr, *dm = nullptr, *dout = nullptr;
+  const size_t bytes = (size_t)(n ? n : 1) * 32;
+  hipError_t e = hipMalloc(&dd, bytes);  // (hipMalloc's alignment covers item_scalars' uint4 loads of w)
+  if (e == hipSuccess) e = hipMalloc(&dr, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dw, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dm, (size_t)(n ? n : 1) * 4);
+  if (e == hipSuccess) e = hipMalloc(&dout, (size_t)(n ? n : 1) * 17 * 4);
+  if (e == hipSuccess && n) e = hipMemcpy(dd, dig, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) e = hipMemcpy(dr, r_be, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) e = hipMemcpy(dw, w, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {
+    uint32_t *im = new uint32_t[n];
+    for (uint32_t i = 0; i < n; i++) im[i] = i;
+    e = hipMemcpy(dm, im, (size_t)n * 4, hipMemcpyHostToDevice);
+    delete[] im;
+  }
+  if (e == hipSuccess && n) {
+    hipLaunchKernelGGL(k_scalars, dim3((n + 255) / 256), dim3(256), 0, 0, n, dd, dr, dw, dm, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess && n) e = hipMemcpy(out, dout, (size_t)n * 17 * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(dd);
+  (void)hipFree(dr);
+  (void)hipFree(dw);
+  (void)hipFree(dm);
+  (void)hipFree(dout);
   return e == hipSuccess ? 0 : -(int)e;
 }

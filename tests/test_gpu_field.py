@@ -160,6 +160,57 @@ def test_sc_mont_matches_python_ints():
     assert not bad, bad[:5]
 
 
+LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72  # phi's eigenvalue mod N
+
+
+def test_item_scalars_match_python_ints():
+    """verify_core.h's item_scalars on the device, one item per lane, against
+    Python integers: u1 = e s^-1 mod N (< N) for the UNREDUCED 256-bit digest
+    e — 0 and N (u1 = 0), k N mod 2^256 for small k (the values a reduction
+    that wraps would confuse), N +- 1, 2^256 - N - 1, 2^256 - 1 and _operands'
+    edge-heavy values — and the GLV halves of u2 = r s^-1 under the sign
+    word, +-k1 +- k2 lambda == u2 (mod N) with k1, k2 < 2^129:
+    sc_load_be_words, sc_mont and glv_split as the kernels chain them, crossed
+    with s in {1, 2, (N - 1) / 2, N - 1, random} and r in {1, N - 1, random}.
+    tests/test_glv_int.py compares glv_split with integers in a host build;
+    this is the device's."""
+    rng = random.Random(77)
+    es = _operands(71, 64)  # the edge list, values near 2^256, limb patterns, random
+    es += [0, N, N - 1, N + 1, 2**256 - N - 1, 2**256 - 1] + [k * N % 2**256 for k in range(2, 10)]
+    cases = []
+    for e in es:
+        for s in (1, 2, (N - 1) // 2, N - 1, rng.randrange(1, N)):
+            for r in (1, N - 1, rng.randrange(1, N)):
+                cases.append((e, r, s))
+    n = len(cases)
+    assert 500 < n < 5000 and n % 256  # more than one block, a ragged last one
+
+    def be(xs):
+        return np.frombuffer(b"".join(x.to_bytes(32, "big") for x in xs), dtype=np.uint32).reshape(len(xs), 8).copy()
+
+    D, R = be([c[0] for c in cases]), be([c[1] for c in cases])
+    W = _pack_fast([pow(c[2], -1, N) * 2**256 % N for c in cases])
+    out = np.zeros((n, 17), np.uint32)
+    L = _lib()
+    L.fc_scalars.argtypes = [ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    L.fc_scalars.restype = ctypes.c_int
+    assert L.fc_scalars(n, D.ctypes.data, R.ctypes.data, W.ctypes.data, out.ctypes.data) == 0
+    u1s = _unpack(out[:, :8])
+    bad = []
+    for i, (e, r, s) in enumerate(cases):
+        si = pow(s, -1, N)
+        k1 = sum(int(out[i, 8 + k]) << (32 * k) for k in range(4))
+        k2 = sum(int(out[i, 12 + k]) << (32 * k) for k in range(4))
+        signs = int(out[i, 16])
+        k1s, k2s = (-k1 if signs & 1 else k1), (-k2 if signs & 2 else k2)
+        ok = (u1s[i] == e * si % N and u1s[i] < N and (k1s + k2s * LAMBDA - r * si) % N == 0
+              and k1 < 2**129 and k2 < 2**129 and signs < 4)
+        if not ok:
+            bad.append((hex(e), hex(r), hex(s), hex(u1s[i]), hex(k1), hex(k2), signs))
+    assert not bad, (len(bad), bad[:3])
+    assert sum(1 for i, (e, _, _) in enumerate(cases) if e % N == 0 and u1s[i] == 0) >= 2 * 15  # e = 0, e = N
+
+
 def test_fe_inv_var_matches_python_ints():
     a, _ = _pairs(2000, 31)
     a = [x for x in a if x % P]

@@ -179,6 +179,13 @@ def test_host_item_record_sanitized(run):
         klen = 65 if i % 13 else rng.choice([0, 33, 64, 66, 100])
         key = bytes([4] + [rng.getrandbits(8) for _ in range(klen - 1)]) if klen else b""
         cases.append((e, r, s, pre, key))
+    # the digest's edge values (e is read unreduced: 0 and N give u1 = 0, e >= N up to 2^256 - 1), crossed with
+    # the r and s choices above
+    key = bytes([4] + [rng.getrandbits(8) for _ in range(64)])
+    for e in (0, 1, N - 1, N, N + 1, 2 ** 256 - N - 1, 2 ** 256 - 1):
+        for r in (0, 1, N - 1, N, 2 ** 256 - 1, rng.getrandbits(256)):
+            for s in (0, 1, 2, N - 1, N, N + 1, 2 ** 256 - 1, rng.randrange(1, N)):
+                cases.append((e, r, s, 0, key))
     out = run([f"R {e:064x} {r:064x} {s:064x} {pre} {key.hex() or '-'}" for e, r, s, pre, key in cases])
 
     def limbs(w, a, n):
