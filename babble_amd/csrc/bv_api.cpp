@@ -168,12 +168,6 @@ int bv_fail(bv_ctx *c, int code, const char *what, hipError_t e) {
   return code;
 }
 
-#define HIPCHK(expr, code, what)                               \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
-  } while (0)
-
 // ---------------------------------------------------------------------------
 // caller-visible pinned memory (bv_host_alloc): a host-entry call whose
 // arrays live in it is DMA'd straight from them, without the staging copy
@@ -479,6 +473,49 @@ hipStream_t bv_copy_stream(bv_ctx *ctx) {
   }
   ctx->cstream = d.cstream;
   return ctx->cstream;
+}
+
+int bv_stage_run(bv_ctx *ctx, const std::vector<StageOp> &ops) {
+  uint8_t *pin = (uint8_t *)ctx->pin_in.p, *dev = ctx->d_in.as<uint8_t>();
+  hipStream_t cs = ctx->cstream;
+  std::vector<CopyPool::Piece> pieces;
+  for (size_t i = 0; i < ops.size(); i++) {
+    const StageOp &op = ops[i];
+    if (op.type == StageOp::POOL_COPY) {
+      pieces.push_back({pin + op.off, op.src, op.n});
+      if (i + 1 == ops.size() || ops[i + 1].type != StageOp::POOL_COPY) {
+        ctx->pool->copy_many(pieces);
+        pieces.clear();
+      }
+    } else if (op.type == StageOp::DMA_CALLER) {
+      HIPCHK(hipMemcpyAsync(dev + op.off, op.src, op.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH,
+             "h2d (pinned caller buffer)");
+    } else {
+      HIPCHK(hipMemcpyAsync(dev + op.off, pin + op.off, op.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
+    }
+  }
+  return BV_OK;
+}
+
+int bv_stage_range(bv_ctx *ctx, const StagePlan &plan, size_t a0, size_t a1, size_t piece) {
+  std::vector<StageOp> ops;
+  plan.range(a0, a1, piece, ops);
+  return bv_stage_run(ctx, ops);
+}
+
+int bv_stage_slices(bv_ctx *ctx, const StagePlan &plan, uint64_t e0, uint64_t e1) {
+  std::vector<StageOp> ops;
+  plan.slices(e0, e1, ops);
+  return bv_stage_run(ctx, ops);
+}
+
+int bv_stage_one_copy(bv_ctx *ctx, const StagePlan &plan) {
+  uint8_t *pin = (uint8_t *)ctx->pin_in.p;
+  for (const StagePlan::Seg &g : plan.segs)
+    if (g.n) memcpy(pin + g.off, g.src, g.n);
+  HIPCHK(hipMemcpyAsync(ctx->d_in.p, pin, plan.total, hipMemcpyHostToDevice, ctx->cstream), BV_E_LAUNCH,
+         "h2d (one copy)");
+  return BV_OK;
 }
 
 // After a failed call: wait for everything this ctx enqueued.  The streams
@@ -1007,12 +1044,7 @@ int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b, bool text) {
     if (b->key_off[k] > b->key_off[k + 1]) return bv_fail(ctx, BV_E_ARGS, "key_off not monotone");
   // the O(n) checks run on the copy pool (1M items: ~0.3 ms instead of ~3)
   constexpr uint64_t kGrain = 1 << 17;
-  if (!ctx->pool->parallel_for(n_msgs, kGrain, [b](uint64_t lo, uint64_t hi) {
-        for (uint64_t m = lo; m < hi; m++)
-          if (b->msg_off[m] > b->msg_off[m + 1]) return false;
-        return true;
-      }))
-    return bv_fail(ctx, BV_E_ARGS, "msg_off not monotone");
+  if (!monotone(ctx->pool, b->msg_off, n_msgs)) return bv_fail(ctx, BV_E_ARGS, "msg_off not monotone");
   if (!ctx->pool->parallel_for(n_items, kGrain, [b, n_msgs, n_keys](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++)
           if (b->item_msg[i] >= n_msgs || b->item_key[i] >= n_keys) return false;
@@ -1055,129 +1087,80 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
       if (b->msg_off[m + 1] - b->msg_off[m] > kHostHashLen) longm.push_back(m);
 
   // one staging layout, identical in pinned host memory and in HBM
-  struct Seg {
-    const void *src;
-    size_t n;
-    size_t off;
-  };
-  Seg segs[9];
-  size_t total = 0;
-  auto add = [&](int i, const void *src, size_t n, size_t pad) {
-    segs[i] = {src, n, total};
-    total += align256(n + pad);
-  };
+  StagePlan plan;
   // staging order: the keys (the key tables start once they land), s and
   // pre (s^-1), the other item arrays, then the message bytes.  With
   // signature text its offsets and bytes take the place of s and pre (the
   // s^-1 stream decodes r, s and pre from them), and r is not staged.
-  add(1, b->key_off, n_keys ? (n_keys + 1) * 8ull : 0, 0);
-  add(2, b->key_bytes, key_len, 64);
-  if (sig) {
-    add(6, sig->off, (n_items + 1) * 8, 0);
-    add(7, sig->text, sig->off[n_items], 0);
-  } else {
-    add(6, b->s_be, n_items * 32, 0);
-    add(7, b->pre, b->pre ? n_items : 0, 0);
-  }
-  add(0, b->msg_off, n_msgs ? (n_msgs + 1) * 8 : 0, 0);
-  add(3, b->item_msg, n_items * 4, 0);
-  add(4, b->item_key, n_items * 4, 0);
-  add(5, b->r_be, sig ? 0 : n_items * 32, 0);
-  add(8, b->msg_bytes, msg_len, 64);
+  const size_t o_koff = plan.add(b->key_off, n_keys ? (n_keys + 1) * 8ull : 0);
+  const size_t o_kb = plan.add(b->key_bytes, key_len, {}, 1, 64);
+  const size_t o_s = sig ? plan.add(sig->off, (n_items + 1) * 8) : plan.add(b->s_be, n_items * 32);
+  const size_t o_pre = sig ? plan.add(sig->text, sig->off[n_items]) : plan.add(b->pre, n_items);
+  const size_t o_moff = plan.add(b->msg_off, n_msgs ? (n_msgs + 1) * 8 : 0);
+  const size_t o_im = plan.add(b->item_msg, n_items * 4);
+  const size_t o_ik = plan.add(b->item_key, n_items * 4);
+  const size_t o_r = plan.add(b->r_be, sig ? 0 : n_items * 32);
+  const size_t o_msg = plan.add(b->msg_bytes, msg_len, {}, 1, 64);  // (the last segment: chunk by chunk, below)
+  const size_t total = plan.total;
   // previous work on this ctx must be done before its staging is reused
   if (bv_wait_all(ctx) != BV_OK) return BV_E_LAUNCH;  // previous calls' work buffers / staging
   HIPCHK(ctx->pin_in.ensure(total), BV_E_OOM, "alloc pinned staging");
   HIPCHK(ctx->d_in.ensure(total), BV_E_OOM, "alloc device staging");
   uint8_t *pin = (uint8_t *)ctx->pin_in.p, *dev = ctx->d_in.as<uint8_t>();
   HIPCHK(hipEventRecord(ctx->S().ev[E_CALL], cs), BV_E_LAUNCH, "event");
-  // arrays in bv_host_alloc memory are DMA'd from where they are
-  bool direct[9];
-  for (int i = 0; i < 9; i++) direct[i] = bv_is_pinned(segs[i].src, segs[i].n);
-  call->direct_in = direct[8];
+  plan.mark_direct(bv_is_pinned);  // arrays in bv_host_alloc memory are DMA'd from where they are
+  const bool direct_msg = plan.direct.back();
+  call->direct_in = direct_msg;
 
-  // keys and item arrays first (one contiguous region of the layout), in
-  // kChunk pieces: the pool fills piece c+1 while the DMA engine moves piece c
   size_t ev_i = 0;
   auto chunk_event = [&]() -> hipEvent_t {
     hipEvent_t e = ctx->chunk_ev[ev_i % ctx->chunk_ev.size()];
     ev_i++;
     return e;
   };
-  // layout bytes [a0, a1) of segments 0-7, in kChunk pieces: the pool fills
-  // piece c+1 while the DMA engine moves piece c
-  auto stage = [&](size_t a0, size_t a1) -> int {
-    for (size_t a = a0; a < a1; a += kChunk) {
-      const size_t z = std::min(a1, a + kChunk);
-      std::vector<CopyPool::Piece> pieces;
-      bool any_direct = false;
-      for (int i = 0; i < 8; i++) {
-        const Seg &s = segs[i];
-        const size_t lo = std::max(a, s.off), hi = std::min(z, s.off + s.n);
-        if (lo >= hi) continue;
-        if (direct[i]) {
-          any_direct = true;
-          HIPCHK(hipMemcpyAsync(dev + lo, (const uint8_t *)s.src + (lo - s.off), hi - lo, hipMemcpyHostToDevice, cs),
-                 BV_E_LAUNCH, "h2d (pinned caller buffer)");
-        } else {
-          pieces.push_back({pin + lo, (const uint8_t *)s.src + (lo - s.off), hi - lo});
-        }
-      }
-      ctx->pool->copy_many(pieces);
-      if (!any_direct) {
-        HIPCHK(hipMemcpyAsync(dev + a, pin + a, z - a, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-      } else {
-        for (const CopyPool::Piece &q : pieces) {
-          const size_t o = (uint8_t *)q.dst - pin;
-          HIPCHK(hipMemcpyAsync(dev + o, q.dst, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-        }
-      }
-    }
-    return BV_OK;
-  };
   // a small batch (every array in pageable memory) crosses in ONE copy: the
   // whole layout, message bytes and their zero pad included
-  bool one_copy = total <= kSmallStage;
-  for (int i = 0; i < 9; i++) one_copy = one_copy && !direct[i];
+  const bool one_copy = total <= kSmallStage && !memchr(plan.direct.data(), 1, plan.direct.size());
   if (one_copy) {
-    for (int i = 0; i < 9; i++)
-      if (segs[i].n) memcpy(pin + segs[i].off, segs[i].src, segs[i].n);
-    if (msg_len) memset(pin + segs[8].off + msg_len, 0, 64);
-    HIPCHK(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d (one copy)");
+    if (msg_len) memset(pin + o_msg + msg_len, 0, 64);
+    if ((rc = bv_stage_one_copy(ctx, plan)) != BV_OK) return rc;
     for (int e : {E_KREADY, E_SREADY, E_SMALL}) HIPCHK(hipEventRecord(ctx->S().ev[e], cs), BV_E_LAUNCH, "event");
   } else {
-    rc = stage(0, segs[6].off);  // the keys
+    // the arrays ahead of the message bytes, in kChunk pieces: the pool fills
+    // piece c+1 while the DMA engine moves piece c
+    rc = bv_stage_range(ctx, plan, 0, o_s, kChunk);  // the keys
     if (rc != BV_OK) return rc;
     HIPCHK(hipEventRecord(ctx->S().ev[E_KREADY], cs), BV_E_LAUNCH, "event");
-    rc = stage(segs[6].off, segs[0].off);  // s, pre
+    rc = bv_stage_range(ctx, plan, o_s, o_moff, kChunk);  // s, pre
     if (rc != BV_OK) return rc;
     HIPCHK(hipEventRecord(ctx->S().ev[E_SREADY], cs), BV_E_LAUNCH, "event");
-    rc = stage(segs[0].off, segs[8].off);  // msg_off, item_msg, item_key, r
+    rc = bv_stage_range(ctx, plan, o_moff, o_msg, kChunk);  // msg_off, item_msg, item_key, r
     if (rc != BV_OK) return rc;
     // zero the message-bytes pad (the SHA kernel over-reads the last dword of
     // a message into it): in the staging, or on the device for direct bytes
-    if (msg_len && !direct[8]) memset(pin + segs[8].off + msg_len, 0, 64);
-    if (msg_len && direct[8])
-      HIPCHK(hipMemsetAsync(dev + segs[8].off + msg_len, 0, 64, cs), BV_E_LAUNCH, "zero message pad");
+    if (msg_len && !direct_msg) memset(pin + o_msg + msg_len, 0, 64);
+    if (msg_len && direct_msg)
+      HIPCHK(hipMemsetAsync(dev + o_msg + msg_len, 0, 64, cs), BV_E_LAUNCH, "zero message pad");
     HIPCHK(hipEventRecord(ctx->S().ev[E_SMALL], cs), BV_E_LAUNCH, "event");
   }
 
   bv_batch d = {};
   d.n_msgs = n_msgs;
-  d.msg_bytes = dev + segs[8].off;
-  d.msg_off = (const uint64_t *)(dev + segs[0].off);
+  d.msg_bytes = dev + o_msg;
+  d.msg_off = (const uint64_t *)(dev + o_moff);
   d.n_keys = n_keys;
-  d.key_bytes = dev + segs[2].off;
-  d.key_off = (const uint64_t *)(dev + segs[1].off);
+  d.key_bytes = dev + o_kb;
+  d.key_off = (const uint64_t *)(dev + o_koff);
   d.n_items = n_items;
-  d.item_msg = (const uint32_t *)(dev + segs[3].off);
-  d.item_key = (const uint32_t *)(dev + segs[4].off);
-  d.r_be = dev + segs[5].off;
-  d.s_be = dev + segs[6].off;
-  d.pre = b->pre ? dev + segs[7].off : nullptr;
+  d.item_msg = (const uint32_t *)(dev + o_im);
+  d.item_key = (const uint32_t *)(dev + o_ik);
+  d.r_be = dev + o_r;
+  d.s_be = dev + o_s;
+  d.pre = b->pre ? dev + o_pre : nullptr;
   bv_sig_text dsig;
   if (sig) {  // decoded on the s^-1 stream (bv_run_keys) into ctx->d_sig
-    dsig.off = (const uint64_t *)(dev + segs[6].off);
-    dsig.text = dev + segs[7].off;
+    dsig.off = (const uint64_t *)(dev + o_s);
+    dsig.text = dev + o_pre;
     bv_sig_out so;
     rc = bv_sig_bufs(ctx, n_items, &so);
     if (rc != BV_OK) return rc;
@@ -1187,12 +1170,8 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
   if (ctx->host_stamps) st_items = stamp_ms();
   // key cache resolution needs the keys on the device (decode of misses)
   bool kc = false;
-  if ((ctx->flags & BV_F_KEY_CACHE) && n_keys && n_keys <= kKcMaxBatchKeys) {
-    HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_KREADY], 0), BV_E_LAUNCH, "join");
-    bv_kc_items items;
-    items.n_items = b->n_items;
-    items.h_item_key = b->item_key;
-    rc = bv_kc_prepare(ctx, n_keys, b->key_bytes, b->key_off, d.key_bytes, d.key_off, st, &kc, false, &items);
+  if (n_keys && n_keys <= kKcMaxBatchKeys) {  // (else `st` does not wait for the keys either)
+    rc = bv_kc_host_step(ctx, b->key_bytes, b->key_off, d, b->item_key, st, &kc);
     if (rc != BV_OK) return rc;
   }
   // the key tables need only the keys and s^-1 only s: they run while the
@@ -1248,15 +1227,15 @@ int bv_host_launch(bv_ctx *ctx, const bv_batch *b, bv_host_call *call, const bv_
     const uint64_t end = b->msg_off[m1];
     if (one_copy) {
       // already on the device
-    } else if (direct[8]) {
-      HIPCHK(hipMemcpyAsync(dev + segs[8].off + base, b->msg_bytes + base, end - base, hipMemcpyHostToDevice, cs),
+    } else if (direct_msg) {
+      HIPCHK(hipMemcpyAsync(dev + o_msg + base, b->msg_bytes + base, end - base, hipMemcpyHostToDevice, cs),
              BV_E_LAUNCH, "h2d msgs (pinned caller buffer)");
     } else {
       const size_t len = end - base + (m1 == n_msgs ? 64 : 0);
       const double c0 = ctx->host_stamps ? stamp_ms() : 0;
-      ctx->pool->copy(pin + segs[8].off + base, b->msg_bytes + base, end - base);
+      ctx->pool->copy(pin + o_msg + base, b->msg_bytes + base, end - base);
       if (ctx->host_stamps) st_copy += stamp_ms() - c0;
-      HIPCHK(hipMemcpyAsync(dev + segs[8].off + base, pin + segs[8].off + base, len, hipMemcpyHostToDevice, cs),
+      HIPCHK(hipMemcpyAsync(dev + o_msg + base, pin + o_msg + base, len, hipMemcpyHostToDevice, cs),
              BV_E_LAUNCH, "h2d msgs");
     }
     hipEvent_t e = chunk_event();
@@ -1630,12 +1609,7 @@ int bv_validate_sig_text(bv_ctx *ctx, uint64_t n_items, const bv_sig_text &sig) 
   if (!sig.off) return bv_fail(ctx, BV_E_ARGS, "null sig_off");
   if (sig.off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "sig_off[0] != 0");
   const uint64_t *off = sig.off;
-  if (!ctx->pool->parallel_for(n_items, 1 << 17, [off](uint64_t lo, uint64_t hi) {
-        for (uint64_t i = lo; i < hi; i++)
-          if (off[i] > off[i + 1]) return false;
-        return true;
-      }))
-    return bv_fail(ctx, BV_E_ARGS, "sig_off not monotone");
+  if (!monotone(ctx->pool, off, n_items)) return bv_fail(ctx, BV_E_ARGS, "sig_off not monotone");
   if (off[n_items] && !sig.text) return bv_fail(ctx, BV_E_ARGS, "null sig_text");
   return BV_OK;
 }

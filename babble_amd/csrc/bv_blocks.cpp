@@ -22,12 +22,6 @@
 #include "bv_internal.h"
 #include "hostsha.h"
 
-#define HIPCHK(expr, code, what)                               \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
-  } while (0)
-
 namespace {
 
 constexpr size_t kChunk = 64ull << 20;  // staged bytes per pinned piece (as bv_events.cpp)
@@ -37,14 +31,6 @@ constexpr uint64_t kGrain = 1 << 17;
 // fn(lo, hi) over [0, n) on the pool (when there is one) and the caller
 bool par(CopyPool *pool, uint64_t n, uint64_t grain, const std::function<bool(uint64_t, uint64_t)> &fn) {
   return pool ? pool->parallel_for(n, grain, fn) : fn(0, n);
-}
-
-bool monotone(CopyPool *pool, const uint64_t *off, uint64_t n) {
-  return par(pool, n, kGrain, [off](uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; i++)
-      if (off[i] > off[i + 1]) return false;
-    return true;
-  });
 }
 
 // The block fields (what blk_len / blk_emit read): nullptr, or what is wrong.
@@ -189,45 +175,35 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   const uint64_t hash_len = k->hash_off[3 * n];
   const uint64_t itx_len = k->itx_off ? k->itx_off[n] : 0, rcpt_len = k->rcpt_off ? k->rcpt_off[n] : 0;
   const uint64_t text_len = text ? k->sig_off[n_items] : 0;
-  struct Seg {
-    const void *src;
-    size_t n, off;
-  };
-  std::vector<Seg> segs;
-  size_t total = 0;
-  auto add = [&](const void *src, size_t bytes, size_t pad = 0) -> size_t {
-    if (!src) bytes = 0;
-    const size_t o = total;
-    segs.push_back({src, bytes, o});
-    total += align256(bytes + pad);
-    return o;
-  };
+  StagePlan plan;
+  auto add = [&](const void *src, size_t bytes, size_t pad = 0) { return plan.add(src, bytes, {}, 1, pad); };
   // the keys; the signature text or s / pre; the item arrays; the block fields
   const size_t o_koff = add(k->key_off, n_keys ? (n_keys + 1) * 8ull : 0);
-  const size_t i_kb = segs.size(), o_kb = add(k->key_bytes, key_len, 64);
-  const size_t keys_end = total;
+  const size_t i_kb = plan.segs.size(), o_kb = add(k->key_bytes, key_len, 64);
+  const size_t keys_end = plan.total;
   const size_t o_s = text ? add(k->sig_off, (n_items + 1) * 8) : add(k->s_be, n_items * 32);
   const size_t o_pre = text ? add(k->sig_text, text_len) : add(k->pre, n_items);
-  const size_t s_end = total;
+  const size_t s_end = plan.total;
   const size_t o_ib = add(k->item_block, n_items * 4);
   const size_t o_ik = add(k->item_key, n_items * 4);
   const size_t o_r = add(text ? nullptr : k->r_be, n_items * 32);
-  const size_t r_end = total;
+  const size_t r_end = plan.total;
   const size_t o_ix = add(k->index, n * 8);
   const size_t o_rr = add(k->round_received, n * 8);
   const size_t o_ts = add(k->timestamp, n * 8);
   const size_t o_ho = add(k->hash_off, (3 * n + 1) * 8);
-  const size_t i_hb = segs.size(), o_hb = add(k->hash_bytes, hash_len, 64);
+  const size_t i_hb = plan.segs.size(), o_hb = add(k->hash_bytes, hash_len, 64);
   const size_t o_hn = add(k->hash_nil, 3 * n);
   const size_t o_txs = add(k->tx_start, (n + 1) * 8);
   const size_t o_txo = add(k->tx_off, n_tx ? (n_tx + 1) * 8 : 0);
-  const size_t i_txb = segs.size(), o_txb = add(k->tx_bytes, tx_len, 64);
+  const size_t i_txb = plan.segs.size(), o_txb = add(k->tx_bytes, tx_len, 64);
   const size_t o_tln = add(k->tx_list_nil, n);
   const size_t o_txn = add(k->tx_nil, n_tx);
   const size_t o_io = add(k->itx_off, (n + 1) * 8);
   const size_t o_ij = add(k->itx_json, itx_len);
   const size_t o_ro = add(k->rcpt_off, (n + 1) * 8);
   const size_t o_rj = add(k->rcpt_json, rcpt_len);
+  const size_t total = plan.total;
 
   if (bv_wait_all(ctx) != BV_OK) return BV_E_LAUNCH;  // previous calls' work buffers / staging
   HIPCHK(ctx->pin_in.ensure(total + 256), BV_E_OOM, "alloc pinned staging");
@@ -237,54 +213,20 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   if (!cs) return bv_fail(ctx, BV_E_NODEVICE, "copy stream");
   hipEvent_t *ev = ctx->S().ev;
   HIPCHK(hipEventRecord(ev[E_CALL], cs), BV_E_LAUNCH, "event");
-  // arrays in bv_host_alloc memory are DMA'd from where they are
-  std::vector<char> direct(segs.size());
-  for (size_t i = 0; i < segs.size(); i++) direct[i] = segs[i].n && bv_is_pinned(segs[i].src, segs[i].n);
-  // layout bytes [a0, a1) in kChunk pieces: the pool fills piece c+1 while the DMA engine moves piece c
-  std::function<int(size_t, size_t)> stage = [&](size_t a0, size_t a1) -> int {
-    for (size_t a = a0; a < a1; a += kChunk) {
-      const size_t z = std::min(a1, a + kChunk);
-      std::vector<CopyPool::Piece> pieces;
-      bool any_direct = false;
-      for (size_t i = 0; i < segs.size(); i++) {
-        const Seg &g = segs[i];
-        const size_t lo = std::max(a, g.off), hi = std::min(z, g.off + g.n);
-        if (lo >= hi) continue;
-        if (direct[i]) {
-          any_direct = true;
-          HIPCHK(hipMemcpyAsync(dev + lo, (const uint8_t *)g.src + (lo - g.off), hi - lo, hipMemcpyHostToDevice, cs),
-                 BV_E_LAUNCH, "h2d (pinned caller buffer)");
-        } else {
-          pieces.push_back({pin + lo, (const uint8_t *)g.src + (lo - g.off), hi - lo});
-        }
-      }
-      ctx->pool->copy_many(pieces);
-      if (!any_direct) {
-        HIPCHK(hipMemcpyAsync(dev + a, pin + a, z - a, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-      } else {  // the staged pieces only: the range also holds direct segments
-        for (const CopyPool::Piece &q : pieces) {
-          const size_t o = (uint8_t *)q.dst - pin;
-          HIPCHK(hipMemcpyAsync(dev + o, q.dst, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-        }
-      }
-    }
-    return BV_OK;
-  };
-
+  plan.mark_direct(bv_is_pinned);  // arrays in bv_host_alloc memory are DMA'd from where they are
+  const std::vector<char> &direct = plan.direct;
   // a batch whose whole layout is at most kSmallStage crosses PCIe as ONE copy
   // (each extra small H2D costs ~20 us of DMA latency on a lone call): every
   // array, pinned or not, is gathered into the staging first
   const bool one_copy = total <= kSmallStage;
   if (one_copy) {
-    std::fill(direct.begin(), direct.end(), 0);
     memset(pin, 0, total);
-    for (const Seg &g : segs)
-      if (g.n) memcpy(pin + g.off, g.src, g.n);
-    HIPCHK(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d (one copy)");
-    stage = [](size_t, size_t) -> int { return BV_OK; };
+    if ((rc = bv_stage_one_copy(ctx, plan)) != BV_OK) return rc;
   }
+  // else layout bytes [a0, a1) in kChunk pieces: the pool fills piece c+1 while the DMA engine moves piece c
+  auto cross = [&](size_t a0, size_t a1) { return one_copy ? BV_OK : bv_stage_range(ctx, plan, a0, a1, kChunk); };
   if (!one_copy && !direct[i_kb]) memset(pin + o_kb + key_len, 0, 64);
-  rc = stage(0, keys_end);  // the keys: key decode and the key tables start once they land
+  rc = cross(0, keys_end);  // the keys: key decode and the key tables start once they land
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_KREADY], cs), BV_E_LAUNCH, "event");
 
@@ -309,21 +251,17 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
     d.r_be = so.r, d.s_be = so.s, d.pre = so.pre;
   }
   bool kc = false;
-  if ((ctx->flags & BV_F_KEY_CACHE) && n_keys && n_keys <= kKcMaxBatchKeys) {
-    HIPCHK(hipStreamWaitEvent(st, ev[E_KREADY], 0), BV_E_LAUNCH, "join");
-    bv_kc_items items;
-    items.n_items = n_items;
-    items.h_item_key = k->item_key;
-    rc = bv_kc_prepare(ctx, n_keys, k->key_bytes, k->key_off, d.key_bytes, d.key_off, st, &kc, false, &items);
+  if (n_keys && n_keys <= kKcMaxBatchKeys) {  // (else `st` does not wait for the keys either)
+    rc = bv_kc_host_step(ctx, k->key_bytes, k->key_off, d, k->item_key, st, &kc);
     if (rc != BV_OK) return rc;
   }
-  rc = stage(keys_end, s_end);  // the signature text, or s and pre: k_sig_decode, s^-1
+  rc = cross(keys_end, s_end);  // the signature text, or s and pre: k_sig_decode, s^-1
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_SREADY], cs), BV_E_LAUNCH, "event");
   rc = bv_run_keys(ctx, &d, ev[E_KREADY], ev[E_SREADY], kc, false, text ? &dsig : nullptr);
   if (rc != BV_OK) return rc;
   if (text) HIPCHK(hipStreamWaitEvent(st, ev[E_SDEC], 0), BV_E_LAUNCH, "join decoded signatures");
-  rc = stage(s_end, r_end);  // item_block, item_key, r: the key part of every item
+  rc = cross(s_end, r_end);  // item_block, item_key, r: the key part of every item
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_RREADY], cs), BV_E_LAUNCH, "event");
   bv_item_pipe pipe{ctx, &d, {}, st, kc};
@@ -349,7 +287,7 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   }
   if (!one_copy && hash_len && !direct[i_hb]) memset(pin + o_hb + hash_len, 0, 64);
   if (!one_copy && tx_len && !direct[i_txb]) memset(pin + o_txb + tx_len, 0, 64);
-  rc = stage(r_end, total);
+  rc = cross(r_end, total);
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_SMALL], cs), BV_E_LAUNCH, "event");
 

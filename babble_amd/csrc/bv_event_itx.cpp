@@ -33,12 +33,6 @@
 #include "hostsha.h"
 #include "bsigjson.h"
 
-#define HIPCHK(expr, code, what)                               \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
-  } while (0)
-
 namespace {
 
 constexpr uint64_t kGrain = 1 << 15;
@@ -48,35 +42,27 @@ bool par(CopyPool *pool, uint64_t n, uint64_t grain, const std::function<bool(ui
   return pool ? pool->parallel_for(n, grain, fn) : fn(0, n);
 }
 
-bool monotone(CopyPool *pool, const uint64_t *off, uint64_t n) {
-  return par(pool, n, kGrain, [off](uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; i++)
-      if (off[i] > off[i + 1]) return false;
-    return true;
-  });
-}
-
 // The ITX fields (what itxjson.h reads): nullptr, or what is wrong.
 const char *check_itx(const bv_event_itx_batch *x, CopyPool *pool) {
   const uint64_t n = x->events.n_events;
   if (x->events.itx_off || x->events.itx_json) return "events.itx_off / itx_json must be NULL (the ITXs come from fields)";
   if (!x->itx_start) return "null itx_start";
   if (x->itx_start[0] != 0) return "itx_start[0] != 0";
-  if (!monotone(pool, x->itx_start, n)) return "itx_start not monotone";
+  if (!monotone(pool, x->itx_start, n, kGrain)) return "itx_start not monotone";
   const uint64_t m = x->itx_start[n];
   if (n > (1ull << 32) || m > (1ull << 32) || n + m > (1ull << 32)) return "more than 2^32 events and ITXs";
   if (!m) return nullptr;
   if (!x->itx_type) return "null itx_type";
   if (!x->itx_str_off) return "null itx_str_off";
   if (x->itx_str_off[0] != 0) return "itx_str_off[0] != 0";
-  if (!monotone(pool, x->itx_str_off, 4 * m)) return "itx_str_off not monotone";
+  if (!monotone(pool, x->itx_str_off, 4 * m, kGrain)) return "itx_str_off not monotone";
   if (x->itx_str_off[4 * m] && !x->itx_str) return "null itx_str";
   return nullptr;
 }
 
 // bsig_check (bsigjson.h) with the offset scans spread over the pool
 const char *check_bsig(const bv_event_fields_batch *f, CopyPool *pool) {
-  return bsig_check(*f, [pool](const uint64_t *off, uint64_t n) { return monotone(pool, off, n); });
+  return bsig_check(*f, [pool](const uint64_t *off, uint64_t n) { return monotone(pool, off, n, kGrain); });
 }
 
 // a fields batch stages bsig_val_off / bsig_val_bytes only when an entry reads them
@@ -96,37 +82,6 @@ void dag_hash(const bv_event_itx_batch *x, const bv_event_fields_batch *f, const
               const std::vector<uint32_t> &level_off, const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
   if (f) bv_host_dag_hash_fields(*f, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, w, digests);
   else bv_host_dag_hash_itx(*x, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, w, digests);
-}
-
-// The event fields the serialiser reads, without a context (the host
-// helpers): bv_verify_events' rules.
-const char *check_event_fields(const bv_event_batch *b) {
-  const uint64_t n = b->n_events;
-  if (!n) return nullptr;
-  if (!b->creator || !b->index || !b->timestamp || !b->parent_kind || !b->parent_ref || !b->tx_start || !b->key_off)
-    return "null event array";
-  if (b->key_off[0] != 0) return "key_off[0] != 0";
-  for (uint32_t k = 0; k < b->n_keys; k++)
-    if (b->key_off[k] > b->key_off[k + 1]) return "key_off not monotone";
-  if (b->key_off[b->n_keys] && !b->key_bytes) return "null key bytes";
-  if (b->tx_start[0] != 0) return "tx_start[0] != 0";
-  if (!monotone(nullptr, b->tx_start, n)) return "tx_start not monotone";
-  const uint64_t n_tx = b->tx_start[n];
-  if (n_tx && (!b->tx_off || b->tx_off[0] != 0 || !monotone(nullptr, b->tx_off, n_tx))) return "bad tx_off";
-  if (n_tx && b->tx_off[n_tx] && !b->tx_bytes) return "null tx bytes";
-  if (b->bsig_off && (b->bsig_off[0] != 0 || !monotone(nullptr, b->bsig_off, n))) return "bad bsig_off";
-  if (b->bsig_off && b->bsig_off[n] && !b->bsig_json) return "null fragment bytes";
-  for (uint64_t e = 0; e < n; e++) {
-    if (b->creator[e] >= b->n_keys) return "creator out of range";
-    for (int p = 0; p < 2; p++) {
-      const uint8_t k = b->parent_kind[2 * e + p];
-      const uint64_t r = b->parent_ref[2 * e + p];
-      if (k > BV_PARENT_EVENT) return "bad parent kind";
-      if (k == BV_PARENT_HASH && (r >= b->n_parent_hashes || !b->parent_hashes)) return "parent hash out of range";
-      if (k == BV_PARENT_EVENT && r >= e) return "an in-batch parent must precede its child";
-    }
-  }
-  return nullptr;
 }
 
 // common.DecodeFromString of ITX i's PubKeyHex into at most kItxKeyMax bytes:
@@ -188,13 +143,7 @@ int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   uint32_t pp[2];
   if (dag) {
     std::vector<uint8_t> evdig(n * 32);
-    const HostParFor pf = [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
-      ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
-        fn(lo, hi);
-        return true;
-      });
-    };
-    dag_hash(x, f, order, level_off, pf, ctx->dag_scratch, evdig.data());
+    dag_hash(x, f, order, level_off, bv_pool_parfor(ctx), ctx->dag_scratch, evdig.data());
     memcpy(moff.data(), ctx->dag_scratch.off.data(), (n + 1) * 8);
   } else {
     for (uint64_t e = 0; e < n; e++) moff[e + 1] = moff[e] + body_len(x, f, e, pp);
@@ -275,25 +224,9 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   ctx->last = st;
 
   // DAG levels over in-batch parents (refs point backwards: one pass), as bv_verify_events
-  std::vector<uint32_t> level, order, level_off;
+  std::vector<uint32_t> order, level_off;
   const bool dag = memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n) != nullptr;
-  if (dag) {
-    level.assign(n, 0);
-    uint32_t nl = 1;
-    for (uint64_t e = 0; e < n; e++) {
-      uint32_t l = 0;
-      for (int p = 0; p < 2; p++)
-        if (eb->parent_kind[2 * e + p] == BV_PARENT_EVENT) l = std::max(l, level[eb->parent_ref[2 * e + p]] + 1);
-      level[e] = l;
-      nl = std::max(nl, l + 1);
-    }
-    level_off.assign(nl + 1, 0);
-    for (uint64_t e = 0; e < n; e++) level_off[level[e] + 1]++;
-    for (uint32_t l = 0; l < nl; l++) level_off[l + 1] += level_off[l];
-    order.resize(n);
-    std::vector<uint32_t> fill(level_off.begin(), level_off.end() - 1);
-    for (uint64_t e = 0; e < n; e++) order[fill[level[e]]++] = (uint32_t)e;
-  }
+  if (dag) bv_dag_levels(*eb, order, level_off);
 
   // the ITX keys: decoded at a fixed stride by the pool, then packed behind
   // the creators' keys, one slot per DISTINCT key: an ITX whose key equals a
@@ -357,32 +290,61 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   const bool bv_bytes = f && bsig_has_bytes(f, nb);
   const uint64_t bv_len = bv_bytes ? f->bsig_val_off[nb] : 0;
   const uint64_t n_ph = eb->parent_hashes ? eb->n_parent_hashes : 0;
-  size_t total = 0;
-  auto at = [&](size_t bytes, size_t pad = 0) {
-    const size_t o = total;
-    total += align256(bytes + pad);
-    return o;
-  };
-  const size_t o_koff = at((K + 1) * 8), o_kb = at(key_len, 64), keys_end = total;
-  const size_t o_soff = at((N + 1) * 8), o_text = at(text_len, 64), s_end = total;
-  const size_t o_ik = at(N * 4);
-  const size_t o_is = at((n + 1) * 8), o_iln = at(x->itx_list_nil ? n : 0), o_ity = at(m);
-  const size_t o_iso = at((4 * m + 1) * 8), o_istr = at(str_len, 64), o_force = at(m);
+  // The fields entry's bulk route, a batch of more than one chunk of events:
+  // the arrays that are indexed by event (or by an event's transactions or
+  // block signatures) cross in event-range slices, chunk by chunk, into the
+  // same one-piece device layout, and each chunk's bodies are hashed and its
+  // items verified while the next chunk crosses (as bv_verify_events' chunks).
+  uint64_t chunk_ev = 1 << 17;
+  if (const char *env = getenv("BV_FIELDS_CHUNK")) chunk_ev = std::max<uint64_t>(64, (strtoull(env, nullptr, 10) + 63) / 64 * 64);
+  const bool chunked = f && !dag && n > chunk_ev;
+  // The fields entry: a large array that lies in bv_host_alloc memory is not
+  // copied into the staging block; the DMA engine reads it where it is (as
+  // bv_verify_events does), and the staging runs around it and around the
+  // sliced arrays cross as one copy each.  The ITX entry stages everything.
+  StagePlan plan({f ? (size_t)256 << 10 : StagePolicy::kNever, true});
+  plan.space[S_TX] = {eb->tx_start, 0};
+  plan.space[S_BS] = {f ? f->bsig_start : nullptr, 0};
+  const auto sl = [chunked](StageKind k) { return chunked ? k : StageKind{}; };  // sliced only on that route
+  const StageKind k_ev = sl({S_ELEM, S_EV}), k_ev1 = sl({S_OFFS, S_EV}), k_tx = sl({S_ELEM, S_TX}), k_tx1 = sl({S_OFFS, S_TX});
+  const StageKind k_bs = sl({S_ELEM, S_BS}), k_bs1 = sl({S_OFFS, S_BS}), k_txb = sl({S_BYTES, S_TX, eb->tx_off});
+  const StageKind k_bsb = sl({S_BYTES, S_BS, f ? f->bsig_sig_off : nullptr}),
+                  k_bvb = sl({S_BYTES, S_BS, f ? f->bsig_val_off : nullptr});
+  // (reserve: bytes the driver fills by hand, or that only the device writes)
+  const size_t o_koff = plan.add(koff.data(), (K + 1) * 8), o_kb = plan.reserve(key_len, 64), keys_end = plan.total;
+  const size_t o_soff = plan.add(soff.data(), (N + 1) * 8);  // the events' text, then the ITXs' (by hand) and the pad
+  const size_t o_text = plan.add(eb->sig_text, ev_text_len, {}, 1, text_len - ev_text_len + 64), s_end = plan.total;
+  const size_t o_ik = plan.reserve(N * 4);
+  const size_t o_is = itx_fields ? plan.add(x->itx_start, (n + 1) * 8, k_ev1, 8) : plan.reserve((n + 1) * 8);
+  const size_t o_iln = plan.add(x->itx_list_nil, n, k_ev, 1), o_ity = plan.add(x->itx_type, m);
+  const size_t o_iso = m ? plan.add(x->itx_str_off, (4 * m + 1) * 8) : plan.reserve(8);
+  const size_t o_istr = plan.add(x->itx_str, str_len, {}, 1, 64), o_force = plan.add(force.data(), m);
   const bool bulk = !dag;  // the event fields cross only when the device builds the bodies
-  const size_t o_ix = at(bulk ? n * 8 : 0), o_ts = at(bulk ? n * 8 : 0), o_pk = at(bulk ? n * 2 : 0);
-  const size_t o_pr = at(bulk ? n * 16 : 0), o_ph = at(bulk ? n_ph * 32 : 0), o_txs = at(bulk ? (n + 1) * 8 : 0);
-  const size_t o_txo = at(bulk && n_tx ? (n_tx + 1) * 8 : 0), o_txb = at(bulk ? tx_len : 0, 64);
-  const size_t o_tln = at(bulk && eb->tx_list_nil ? n : 0), o_txn = at(bulk && eb->tx_nil ? n_tx : 0);
-  const size_t o_bo = at(bulk && eb->bsig_off ? (n + 1) * 8 : 0), o_bj = at(bulk ? bsig_len : 0);
+  const size_t o_ix = plan.add(eb->index, bulk ? n * 8 : 0, k_ev, 8), o_ts = plan.add(eb->timestamp, bulk ? n * 8 : 0, k_ev, 8);
+  const size_t o_pk = plan.add(eb->parent_kind, bulk ? n * 2 : 0, k_ev, 2);
+  const size_t o_pr = plan.add(eb->parent_ref, bulk ? n * 16 : 0, k_ev, 16);
+  const size_t o_ph = plan.add(eb->parent_hashes, bulk ? n_ph * 32 : 0);
+  const size_t o_txs = plan.add(eb->tx_start, bulk ? (n + 1) * 8 : 0, k_ev1, 8);
+  const size_t o_txo = plan.add(eb->tx_off, bulk && n_tx ? (n_tx + 1) * 8 : 0, k_tx1, 8);
+  const size_t o_txb = plan.add(eb->tx_bytes, bulk ? tx_len : 0, k_txb, 1, 64);
+  const size_t o_tln = plan.add(eb->tx_list_nil, bulk ? n : 0, k_ev, 1), o_txn = plan.add(eb->tx_nil, bulk ? n_tx : 0, k_tx, 1);
+  const size_t o_bo = plan.add(eb->bsig_off, bulk ? (n + 1) * 8 : 0), o_bj = plan.add(eb->bsig_json, bulk ? bsig_len : 0);
   const bool bf = bulk && f;
-  const size_t o_fs = at(bf ? (n + 1) * 8 : 0), o_fln = at(bf && f->bsig_list_nil ? n : 0), o_fix = at(bf ? nb * 8 : 0);
-  const size_t o_fso = at(bf ? (nb + 1) * 8 : 0), o_fsg = at(bf ? bs_len : 0, 64);
-  const size_t o_fk = at(bf && f->bsig_val_kind ? nb : 0), o_fvo = at(bf && bv_bytes ? (nb + 1) * 8 : 0);
-  const size_t o_fvb = at(bf ? bv_len : 0, 64);
-  const size_t in_end = total;
-  const size_t o_dig = at(dag ? n * 32 : 0);  // (pinned side only: the host's digests)
+  const bv_event_fields_batch none = {}, &g = bf ? *f : none;  // (no block-signature field crosses otherwise)
+  // an array whose place does not depend on its presence: the bytes are reserved when it is absent
+  const auto fld = [&](const void *src, size_t bytes, StageKind k, size_t unit, size_t pad = 0) {
+    return src ? plan.add(src, bf ? bytes : 0, k, unit, pad) : plan.reserve(bf ? bytes : 0, pad);
+  };
+  const size_t o_fs = fld(g.bsig_start, (n + 1) * 8, k_ev1, 8), o_fln = plan.add(g.bsig_list_nil, n, k_ev, 1);
+  const size_t o_fix = fld(g.bsig_index, nb * 8, k_bs, 8), o_fso = fld(g.bsig_sig_off, (nb + 1) * 8, k_bs1, 8);
+  const size_t o_fsg = fld(g.bsig_sig, bs_len, k_bsb, 1, 64), o_fk = plan.add(g.bsig_val_kind, nb, k_bs, 1);
+  const size_t o_fvo = plan.add(bv_bytes ? g.bsig_val_off : nullptr, (nb + 1) * 8, k_bs1, 8);
+  const size_t o_fvb = fld(g.bsig_val_bytes, bv_len, k_bvb, 1, 64);
+  const size_t in_end = plan.total;
+  const size_t o_dig = plan.reserve(dag ? n * 32 : 0);  // (pinned side only: the host's digests)
   // device side only: k_ev_compose's outputs
-  const size_t o_evst = at(n), o_dby = at(n * 4), o_bits = at((n + 63) / 64 * 8), o_ist = at(m);
+  const size_t o_evst = plan.reserve(n), o_dby = plan.reserve(n * 4), o_bits = plan.reserve((n + 63) / 64 * 8);
+  const size_t o_ist = plan.reserve(m), total = plan.total;
 
   if (bv_wait_all(ctx) != BV_OK) return BV_E_LAUNCH;  // previous calls' work buffers / staging
   HIPCHK(ctx->pin_in.ensure(total), BV_E_OOM, "alloc pinned staging");
@@ -393,61 +355,11 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   if (!cs) return bv_fail(ctx, BV_E_NODEVICE, "copy stream");
   hipEvent_t *ev = ctx->S().ev;
   HIPCHK(hipEventRecord(ev[E_CALL], cs), BV_E_LAUNCH, "event");
-  // The fields entry: a large array that lies in bv_host_alloc memory is not
-  // copied into the staging block; the DMA engine reads it where it is (as
-  // bv_verify_events does), and the staging range around it goes in pieces.
-  struct Direct {
-    size_t o;
-    const void *src;
-    size_t n;
-  };
-  constexpr size_t kDirectMin = 256 << 10;
-  std::vector<Direct> directs;
-  // The fields entry's bulk route, a batch of more than one chunk of events:
-  // the arrays that are indexed by event (or by an event's transactions or
-  // block signatures) cross in event-range slices, chunk by chunk, into the
-  // same one-piece device layout, and each chunk's bodies are hashed and its
-  // items verified while the next chunk crosses (as bv_verify_events' chunks).
-  // A sliced array is left out of the one-piece copies (Direct with no source).
-  enum SliceKind { S_ALL, S_EV, S_EVP1, S_TX, S_TXP1, S_TXB, S_BS, S_BSP1, S_BSB, S_BVB };
-  struct Slice {
-    size_t o;
-    const uint8_t *src;
-    size_t elem;
-    int kind;
-    bool direct;
-  };
-  uint64_t chunk_ev = 1 << 17;
-  if (const char *env = getenv("BV_FIELDS_CHUNK")) chunk_ev = std::max<uint64_t>(64, (strtoull(env, nullptr, 10) + 63) / 64 * 64);
-  const bool chunked = f && !dag && n > chunk_ev;
-  std::vector<Slice> slices;
-  auto put = [&](size_t o, const void *src, size_t bytes, int kind = S_ALL, size_t elem = 1) {
-    if (!bytes || !src) return;
-    const bool direct = f && bytes >= kDirectMin && bv_is_pinned(src, bytes);
-    if (chunked && kind != S_ALL) {
-      slices.push_back({o, (const uint8_t *)src, elem, kind, direct});
-      directs.push_back({o, nullptr, bytes});
-    } else if (direct) {
-      directs.push_back({o, src, bytes});
-    } else {
-      ctx->pool->copy(pin + o, src, bytes);
-    }
-  };
-  auto h2d = [&](size_t a, size_t z) -> int {
-    std::sort(directs.begin(), directs.end(), [](const Direct &x, const Direct &y) { return x.o < y.o; });
-    size_t at = a;
-    for (const Direct &d : directs) {  // (every one lies in [a, z): they are taken out below)
-      if (d.o > at) HIPCHK(hipMemcpyAsync(dev + at, pin + at, d.o - at, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-      if (d.src) HIPCHK(hipMemcpyAsync(dev + d.o, d.src, d.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d in place");
-      at = d.o + d.n;
-    }
-    directs.clear();
-    if (z > at) HIPCHK(hipMemcpyAsync(dev + at, pin + at, z - at, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-    return BV_OK;
-  };
+  plan.mark_direct(bv_is_pinned);
+  // each phase as one piece: the planned arrays into the staging block, then the copies in layout order
+  auto h2d = [&](size_t a, size_t z) { return bv_stage_range(ctx, plan, a, z, z - a); };
 
   // the keys
-  put(o_koff, koff.data(), (K + 1) * 8);
   if (ev_key_len) memcpy(pin + o_kb, eb->key_bytes, ev_key_len);  // (always staged: the key cache reads them here)
   for (size_t u = 0; u < usrc.size(); u++) {
     const uint64_t a = koff[n_keys + u], len = koff[n_keys + u + 1] - a;
@@ -471,19 +383,12 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   vb.item_msg = ctx->ev_iota.as<uint32_t>();
   vb.item_key = (const uint32_t *)(dev + o_ik);
   bool kc = false;
-  if ((ctx->flags & BV_F_KEY_CACHE) && K <= kKcMaxBatchKeys) {
-    HIPCHK(hipStreamWaitEvent(st, ev[E_KREADY], 0), BV_E_LAUNCH, "join");
-    bv_kc_items items;
-    items.n_items = N;
-    items.h_item_key = h_ik;
-    rc = bv_kc_prepare(ctx, (uint32_t)K, pin + o_kb, (const uint64_t *)(pin + o_koff), vb.key_bytes, vb.key_off, st,
-                       &kc, false, &items);
+  if (K <= kKcMaxBatchKeys) {  // (else `st` does not wait for the keys either)
+    rc = bv_kc_host_step(ctx, pin + o_kb, (const uint64_t *)(pin + o_koff), vb, h_ik, st, &kc);
     if (rc != BV_OK) return rc;
   }
 
   // the signature text: r, s and pre of every item decoded on the device
-  put(o_soff, soff.data(), (N + 1) * 8);
-  put(o_text, eb->sig_text, ev_text_len);
   if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; i++) {
       const uint64_t len = soff[n + i + 1] - soff[n + i];
@@ -501,41 +406,10 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   rc = bv_run_keys(ctx, &vb, ev[E_KREADY], ev[E_SREADY], kc);
   if (rc != BV_OK) return rc;
 
-  // the fields
-  if (itx_fields) put(o_is, x->itx_start, (n + 1) * 8, S_EVP1);
-  if (x->itx_list_nil) put(o_iln, x->itx_list_nil, n, S_EV, 1);
-  put(o_ity, x->itx_type, m);
-  if (m) put(o_iso, x->itx_str_off, (4 * m + 1) * 8);
-  put(o_istr, x->itx_str, str_len);
+  // the fields (and the pads the serialisers' last reads run into)
   memset(pin + o_istr + str_len, 0, 64);
-  put(o_force, force.data(), m);
-  if (bulk) {
-    put(o_ix, eb->index, n * 8, S_EV, 8);
-    put(o_ts, eb->timestamp, n * 8, S_EV, 8);
-    put(o_pk, eb->parent_kind, n * 2, S_EV, 2);
-    put(o_pr, eb->parent_ref, n * 16, S_EV, 16);
-    put(o_ph, eb->parent_hashes, n_ph * 32);
-    put(o_txs, eb->tx_start, (n + 1) * 8, S_EVP1);
-    if (n_tx) put(o_txo, eb->tx_off, (n_tx + 1) * 8, S_TXP1);
-    put(o_txb, eb->tx_bytes, tx_len, S_TXB);
-    memset(pin + o_txb + tx_len, 0, 64);
-    if (eb->tx_list_nil) put(o_tln, eb->tx_list_nil, n, S_EV, 1);
-    if (eb->tx_nil) put(o_txn, eb->tx_nil, n_tx, S_TX, 1);
-    if (eb->bsig_off) put(o_bo, eb->bsig_off, (n + 1) * 8);
-    put(o_bj, eb->bsig_json, bsig_len);
-  }
-  if (bf) {
-    put(o_fs, f->bsig_start, (n + 1) * 8, S_EVP1);
-    if (f->bsig_list_nil) put(o_fln, f->bsig_list_nil, n, S_EV, 1);
-    put(o_fix, f->bsig_index, nb * 8, S_BS, 8);
-    put(o_fso, f->bsig_sig_off, (nb + 1) * 8, S_BSP1);
-    put(o_fsg, f->bsig_sig, bs_len, S_BSB);
-    memset(pin + o_fsg + bs_len, 0, 64);
-    if (f->bsig_val_kind) put(o_fk, f->bsig_val_kind, nb, S_BS, 1);
-    if (bv_bytes) put(o_fvo, f->bsig_val_off, (nb + 1) * 8, S_BSP1);
-    put(o_fvb, f->bsig_val_bytes, bv_len, S_BVB);
-    memset(pin + o_fvb + bv_len, 0, 64);
-  }
+  if (bulk) memset(pin + o_txb + tx_len, 0, 64);
+  if (bf) memset(pin + o_fsg + bs_len, 0, 64), memset(pin + o_fvb + bv_len, 0, 64);
   if ((rc = h2d(s_end, in_end)) != BV_OK) return rc;
   HIPCHK(hipEventRecord(ev[E_SMALL], cs), BV_E_LAUNCH, "event");
   HIPCHK(hipStreamWaitEvent(st, ev[E_SMALL], 0), BV_E_LAUNCH, "join");
@@ -594,33 +468,8 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   if (chunked) {
     for (uint64_t a = 0; a < n; a += chunk_ev) {
       const uint64_t z = std::min(n, a + chunk_ev);
-      const uint64_t t0 = eb->tx_start[a], t1 = eb->tx_start[z], j0 = f->bsig_start[a], j1 = f->bsig_start[z];
-      std::vector<CopyPool::Piece> pieces;
-      for (const Slice &g : slices) {
-        size_t lo = 0, hi = 0;
-        switch (g.kind) {
-          case S_EV: lo = a * g.elem, hi = z * g.elem; break;
-          case S_EVP1: lo = a * 8, hi = (z + 1) * 8; break;
-          case S_TX: lo = t0 * g.elem, hi = t1 * g.elem; break;
-          case S_TXP1: lo = t0 * 8, hi = (t1 + 1) * 8; break;
-          case S_TXB: lo = eb->tx_off[t0], hi = eb->tx_off[t1]; break;
-          case S_BS: lo = j0 * g.elem, hi = j1 * g.elem; break;
-          case S_BSP1: lo = j0 * 8, hi = (j1 + 1) * 8; break;
-          case S_BSB: lo = f->bsig_sig_off[j0], hi = f->bsig_sig_off[j1]; break;
-          case S_BVB: lo = f->bsig_val_off[j0], hi = f->bsig_val_off[j1]; break;
-        }
-        if (lo >= hi) continue;
-        if (g.direct)
-          HIPCHK(hipMemcpyAsync(dev + g.o + lo, g.src + lo, hi - lo, hipMemcpyHostToDevice, cs), BV_E_LAUNCH,
-                 "h2d (pinned caller buffer)");
-        else
-          pieces.push_back({pin + g.o + lo, g.src + lo, hi - lo});
-      }
-      ctx->pool->copy_many(pieces);  // the rest of the chunk into pinned memory, then its DMA
-      for (const CopyPool::Piece &q : pieces) {
-        const size_t o = (uint8_t *)q.dst - pin;
-        HIPCHK(hipMemcpyAsync(dev + o, pin + o, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-      }
+      // pinned arrays' slices by DMA from where they lie, the rest into pinned memory, then its DMA
+      if ((rc = bv_stage_slices(ctx, plan, a, z)) != BV_OK) return rc;
       hipEvent_t landed = ctx->chunk_ev[(a / chunk_ev) % ctx->chunk_ev.size()];
       HIPCHK(hipEventRecord(landed, cs), BV_E_LAUNCH, "event");
       HIPCHK(hipStreamWaitEvent(st, landed, 0), BV_E_LAUNCH, "join chunk");
@@ -633,13 +482,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
     HIPCHK(bvk::ev_body_hash_itx(st, dx, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_itx");
   } else {
     // the host's part, beside the device's key / s^-1 work and the ITX hashing
-    const HostParFor pf = [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
-      ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
-        fn(lo, hi);
-        return true;
-      });
-    };
-    dag_hash(x, f, order, level_off, pf, ctx->dag_scratch, pin + o_dig);
+    dag_hash(x, f, order, level_off, bv_pool_parfor(ctx), ctx->dag_scratch, pin + o_dig);
     HIPCHK(hipMemcpyAsync(dig, pin + o_dig, n * 32, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d digests");
   }
   HIPCHK(hipEventRecord(ev[E_STAGED], cs), BV_E_LAUNCH, "event");
@@ -743,7 +586,7 @@ extern "C" int bv_itx_bodies(const bv_event_itx_batch *x, const uint64_t *off, u
 
 extern "C" int bv_event_itx_body_lens(const bv_event_itx_batch *x, uint64_t *off) {
   if (!x || !off) return BV_E_ARGS;
-  if (check_event_fields(&x->events) || check_itx(x, nullptr)) return BV_E_ARGS;
+  if (bv_check_event_fields(&x->events, nullptr, false) || check_itx(x, nullptr)) return BV_E_ARGS;
   const uint64_t n = x->events.n_events;
   off[0] = 0;
   uint32_t pp[2];
@@ -754,7 +597,7 @@ extern "C" int bv_event_itx_body_lens(const bv_event_itx_batch *x, uint64_t *off
 
 extern "C" int bv_event_itx_bodies(const bv_event_itx_batch *x, const uint64_t *off, uint8_t *out) {
   if (!x || !off) return BV_E_ARGS;
-  if (check_event_fields(&x->events) || check_itx(x, nullptr)) return BV_E_ARGS;
+  if (bv_check_event_fields(&x->events, nullptr, false) || check_itx(x, nullptr)) return BV_E_ARGS;
   const uint64_t n = x->events.n_events;
   uint32_t pp[2];
   for (uint64_t e = 0; e < n; e++)
@@ -813,7 +656,7 @@ extern "C" int bv_verify_events_fields(bv_ctx *ctx, const bv_event_fields_batch 
 
 // The fields the serialiser reads, without a context
 static const char *check_fields_host(const bv_event_fields_batch *f) {
-  if (const char *why = check_event_fields(&f->ev.events)) return why;
+  if (const char *why = bv_check_event_fields(&f->ev.events, nullptr, false)) return why;
   if (f->ev.events.itx_off || f->ev.events.itx_json) return "fragment";
   if (f->ev.itx_start)
     if (const char *why = check_itx(&f->ev, nullptr)) return why;

@@ -19,12 +19,6 @@
 #include "bv_internal.h"
 #include "evjson.h"
 
-#define HIPCHK(expr, code, what)                               \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
-  } while (0)
-
 namespace {
 
 // staged bytes per PCIe piece / event chunk: 64 MB (~250k C2 events) keeps
@@ -35,69 +29,12 @@ namespace {
 constexpr size_t kChunk = 64ull << 20;
 constexpr uint64_t kEvTailMin = 65536;  // events: the smallest chunk the halving tail splits off
 
-int validate(bv_ctx *ctx, const bv_event_batch *b) {
-  const uint64_t n = b->n_events;
-  if (!n) return BV_OK;
-  if (!b->creator || !b->index || !b->timestamp || !b->parent_kind || !b->parent_ref || !b->tx_start ||
-      (!b->sig_text && (!b->r_be || !b->s_be)) || !b->key_off)
-    return bv_fail(ctx, BV_E_ARGS, "null event array");
-  if (b->sig_text) {  // signature text: offsets from 0, monotone
-    if (!b->sig_off || b->sig_off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "sig_off missing or sig_off[0] != 0");
-    if (!ctx->pool->parallel_for(n, 1 << 17, [b](uint64_t lo, uint64_t hi) {
-          for (uint64_t e = lo; e < hi; e++)
-            if (b->sig_off[e] > b->sig_off[e + 1]) return false;
-          return true;
-        }))
-      return bv_fail(ctx, BV_E_ARGS, "sig_off not monotone");
-  }
-  if (b->key_off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "key_off[0] != 0");
-  for (uint32_t k = 0; k < b->n_keys; k++)
-    if (b->key_off[k] > b->key_off[k + 1]) return bv_fail(ctx, BV_E_ARGS, "key_off not monotone");
-  if (b->key_off[b->n_keys] && !b->key_bytes) return bv_fail(ctx, BV_E_ARGS, "null key bytes");
-  if (b->tx_start[0] != 0) return bv_fail(ctx, BV_E_ARGS, "tx_start[0] != 0");
-  const uint64_t n_tx = b->tx_start[n];
-  if (n_tx && !b->tx_off) return bv_fail(ctx, BV_E_ARGS, "null tx_off");
-  if (n_tx && b->tx_off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "tx_off[0] != 0");
-  constexpr uint64_t kGrain = 1 << 17;
-  if (!ctx->pool->parallel_for(n_tx, kGrain, [b](uint64_t lo, uint64_t hi) {
-        for (uint64_t t = lo; t < hi; t++)
-          if (b->tx_off[t] > b->tx_off[t + 1]) return false;
-        return true;
-      }))
-    return bv_fail(ctx, BV_E_ARGS, "tx_off not monotone");
-  if (n_tx && b->tx_off[n_tx] && !b->tx_bytes) return bv_fail(ctx, BV_E_ARGS, "null tx bytes");
-  for (const uint64_t *off : {b->itx_off, b->bsig_off})
-    if (off && off[0] != 0) return bv_fail(ctx, BV_E_ARGS, "fragment offsets must start at 0");
-  if ((b->itx_off && b->itx_off[n] && !b->itx_json) || (b->bsig_off && b->bsig_off[n] && !b->bsig_json))
-    return bv_fail(ctx, BV_E_ARGS, "null fragment bytes");
-  for (const uint64_t *off : {b->itx_off, b->bsig_off})
-    if (off && !ctx->pool->parallel_for(n, kGrain, [off](uint64_t lo, uint64_t hi) {
-          for (uint64_t e = lo; e < hi; e++)
-            if (off[e] > off[e + 1]) return false;
-          return true;
-        }))
-      return bv_fail(ctx, BV_E_ARGS, "fragment offsets not monotone");
-  if (!ctx->pool->parallel_for(n, kGrain, [b](uint64_t lo, uint64_t hi) {
-        for (uint64_t e = lo; e < hi; e++) {
-          if (b->creator[e] >= b->n_keys || b->tx_start[e] > b->tx_start[e + 1]) return false;
-          for (int p = 0; p < 2; p++) {
-            const uint8_t k = b->parent_kind[2 * e + p];
-            const uint64_t r = b->parent_ref[2 * e + p];
-            if (k > BV_PARENT_EVENT) return false;
-            if (k == BV_PARENT_HASH && (r >= b->n_parent_hashes || !b->parent_hashes)) return false;
-            if (k == BV_PARENT_EVENT && r >= e) return false;  // an in-batch parent precedes its child
-          }
-        }
-        return true;
-      }))
-    return bv_fail(ctx, BV_E_ARGS,
-                   "bad event reference (creator, tx_start, or a parent not earlier in the batch / out of range)");
-  return BV_OK;
-}
-
 }  // namespace
 
-int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb) { return validate(ctx, eb); }
+int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb) {
+  const char *why = bv_check_event_fields(eb, ctx->pool, true);
+  return why ? bv_fail(ctx, BV_E_ARGS, why) : BV_OK;
+}
 
 static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *res);
 
@@ -159,14 +96,8 @@ static int verify_events_dag_host(bv_ctx *ctx, const bv_event_batch *eb, bv_resu
   vb.s_be = dev + o_s;
   vb.pre = eb->pre ? dev + o_pre : nullptr;
   bool kc = false;
-  if (ctx->flags & BV_F_KEY_CACHE) {
-    HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_KREADY], 0), BV_E_LAUNCH, "join");
-    bv_kc_items items;
-    items.n_items = eb->n_events;
-    items.h_item_key = eb->creator;
-    rc = bv_kc_prepare(ctx, eb->n_keys, eb->key_bytes, eb->key_off, vb.key_bytes, vb.key_off, st, &kc, false, &items);
-    if (rc != BV_OK) return rc;
-  }
+  rc = bv_kc_host_step(ctx, eb->key_bytes, eb->key_off, vb, eb->creator, st, &kc);
+  if (rc != BV_OK) return rc;
   if (text) {
     put(o_s, eb->sig_off, (n + 1) * 8);
     put(o_pre, eb->sig_text, text_len);
@@ -194,14 +125,8 @@ static int verify_events_dag_host(bv_ctx *ctx, const bv_event_batch *eb, bv_resu
   HIPCHK(hipEventRecord(ctx->S().ev[E_FORK], st), BV_E_LAUNCH, "event");
 
   // the host's part, overlapping the device's key / s^-1 work
-  const HostParFor pf = [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
-    ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
-      fn(lo, hi);
-      return true;
-    });
-  };
-  bv_host_dag_hash(*eb, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, pf, ctx->dag_scratch,
-                   pin + o_dig);
+  bv_host_dag_hash(*eb, order.data(), level_off.data(), (uint32_t)level_off.size() - 1, bv_pool_parfor(ctx),
+                   ctx->dag_scratch, pin + o_dig);
   if ((rc = h2d(o_dig, o_dig + n * 32)) != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_STAGED], cs), BV_E_LAUNCH, "event");
   call.ms_prep = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - call.t0).count();
@@ -247,7 +172,7 @@ extern "C" int bv_verify_events(bv_ctx *ctx, const bv_event_batch *eb, bv_result
 static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *res) {
   bv_host_call call;
   call.t0 = std::chrono::steady_clock::now();
-  int rc = validate(ctx, eb);
+  int rc = bv_validate_events(ctx, eb);
   if (rc != BV_OK) return rc;
   ctx->timing = bv_timing{};
   const uint64_t n = eb->n_events;
@@ -256,24 +181,9 @@ static int verify_events_impl(bv_ctx *ctx, const bv_event_batch *eb, bv_result *
   if (n == 0) return BV_OK;
 
   // DAG levels over in-batch parents (refs point backwards: one pass)
-  std::vector<uint32_t> level, order, level_off;
-  const bool dag = memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n) != nullptr;
-  if (dag) {
-    level.assign(n, 0);
-    uint32_t nl = 1;
-    for (uint64_t e = 0; e < n; e++) {
-      uint32_t l = 0;
-      for (int p = 0; p < 2; p++)
-        if (eb->parent_kind[2 * e + p] == BV_PARENT_EVENT) l = std::max(l, level[eb->parent_ref[2 * e + p]] + 1);
-      level[e] = l;
-      nl = std::max(nl, l + 1);
-    }
-    level_off.assign(nl + 1, 0);
-    for (uint64_t e = 0; e < n; e++) level_off[level[e] + 1]++;
-    for (uint32_t l = 0; l < nl; l++) level_off[l + 1] += level_off[l];
-    order.resize(n);
-    std::vector<uint32_t> fill(level_off.begin(), level_off.end() - 1);
-    for (uint64_t e = 0; e < n; e++) order[fill[level[e]]++] = (uint32_t)e;
+  if (memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n)) {
+    std::vector<uint32_t> order, level_off;
+    bv_dag_levels(*eb, order, level_off);
     return verify_events_dag_host(ctx, eb, res, order, level_off, call);
   }
 
@@ -344,84 +254,53 @@ int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard
   const uint64_t key_len = eb->key_off[eb->n_keys];
   const uint64_t itx_len = eb->itx_off ? eb->itx_off[n] - bs.itx : 0,
                  bsig_len = eb->bsig_off ? eb->bsig_off[n] - bs.bsig : 0;
-  // How a segment splits over an event chunk [e0, e1): ALL = whole, in the
-  // first part; EV = `unit` bytes per event; EV1 = an n + 1 offset array
-  // (elements e0 ..= e1); TX / TX1 = the same per transaction of the chunk's
-  // events; TXB / ITX / BSIG = the chunk's bytes of tx_bytes / itx_json /
-  // bsig_json.
-  enum Kind { ALL, EV, EV1, TX, TX1, TXB, ITX, BSIG };
-  struct Seg {
-    const void *src;
-    size_t n, off;
-    Kind kind;
-    size_t unit;
-  };
-  std::vector<Seg> segs;
-  size_t total = 0;
-  auto add = [&](const void *src, size_t bytes, Kind kind, size_t unit = 1, size_t pad = 0) -> size_t {
-    segs.push_back({src, bytes, total, kind, unit});
-    const size_t o = total;
-    total += align256(bytes + pad);
-    return o;
-  };
+  // How a segment splits over an event chunk (hoststage.h): whole, in the
+  // first part; per event or per transaction of the chunk's events (the
+  // shard's transactions start at bs.tx); or the chunk's bytes of tx_bytes /
+  // itx_json / bsig_json through the whole batch's offsets
+  StagePlan plan;
+  plan.space[S_TX] = {eb->tx_start, bs.tx};
+  const StageKind ev{S_ELEM, S_EV}, ev1{S_OFFS, S_EV}, tx{S_ELEM, S_TX}, tx1{S_OFFS, S_TX};
+  const StageKind txb{S_BYTES, S_TX, n_tx ? eb->tx_off : nullptr, bs.txb};
+  const StageKind itxb{S_BYTES, S_EV, eb->itx_off, bs.itx}, bsigb{S_BYTES, S_EV, eb->bsig_off, bs.bsig};
   // keys first (the key tables start once they land), then s and pre (s^-1)
   // and the parent hashes (any event may name any of them); the per-event
   // fields, r and the creators among them, follow chunk by chunk (each
   // chunk's bodies are hashed and its items verified while the next one
   // crosses PCIe)
-  const size_t o_koff = add(eb->key_off, (eb->n_keys + 1) * 8ull, ALL);
-  const size_t o_kb = add(eb->key_bytes, key_len, ALL, 1, 64);
-  const size_t keys_end = total;
+  const size_t o_koff = plan.add(eb->key_off, (eb->n_keys + 1) * 8ull);
+  const size_t o_kb = plan.add(eb->key_bytes, key_len, {}, 1, 64);
+  const size_t keys_end = plan.total;
   // s and pre, or the signature text (decoded on the device into r, s, pre)
   const bool text = eb->sig_text != nullptr;
-  const size_t o_s = text ? add(eb->sig_off, (n + 1) * 8, ALL) : add(eb->s_be, n * 32, ALL);
-  const size_t o_pre = text ? add(eb->sig_text, eb->sig_off[n] - sig_base, ALL) : add(eb->pre, eb->pre ? n : 0, ALL);
-  const size_t s_end = total;
+  const size_t o_s = text ? plan.add(eb->sig_off, (n + 1) * 8) : plan.add(eb->s_be, n * 32);
+  const size_t o_pre = text ? plan.add(eb->sig_text, eb->sig_off[n] - sig_base) : plan.add(eb->pre, n);
+  const size_t s_end = plan.total;
   // key part first (ctx->qfirst): r and the creators cross before the
   // chunks, so every item's k1 Q + k2 phi(Q) is summed under the transfer
   // of the bodies and only u1 G waits for each chunk's digests
   const bool qf = ctx->qfirst;
-  const size_t o_r = qf && !text ? add(eb->r_be, n * 32, ALL) : 0;
-  const size_t o_cr = qf ? add(eb->creator, n * 4, ALL) : 0;
-  const size_t r_end = total;
-  const size_t o_ph = add(eb->parent_hashes, eb->parent_hashes ? eb->n_parent_hashes * 32 : 0, ALL);
-  const size_t small_end = total;
-  const size_t o_r_ev = qf || text ? o_r : add(eb->r_be, n * 32, EV, 32);
-  const size_t o_cr_ev = qf ? o_cr : add(eb->creator, n * 4, EV, 4);
-  const size_t o_ix = add(eb->index, n * 8, EV, 8);
-  const size_t o_ts = add(eb->timestamp, n * 8, EV, 8);
-  const size_t o_pk = add(eb->parent_kind, n * 2, EV, 2);
-  const size_t o_pr = add(eb->parent_ref, n * 16, EV, 16);
-  const size_t o_txs = add(eb->tx_start, (n + 1) * 8, EV1, 8);
-  const size_t o_txo = add(eb->tx_off, n_tx ? (n_tx + 1) * 8 : 0, TX1, 8);
-  const size_t o_txb = add(eb->tx_bytes, tx_len, TXB, 1, 64);
-  const size_t o_tln = add(eb->tx_list_nil, eb->tx_list_nil ? n : 0, EV, 1);
-  const size_t o_txn = add(eb->tx_nil, eb->tx_nil ? n_tx : 0, TX, 1);
-  const size_t o_io = add(eb->itx_off, eb->itx_off ? (n + 1) * 8 : 0, EV1, 8);
-  const size_t o_ij = add(eb->itx_json, itx_len, ITX);
-  const size_t o_bo = add(eb->bsig_off, eb->bsig_off ? (n + 1) * 8 : 0, EV1, 8);
-  const size_t o_bj = add(eb->bsig_json, bsig_len, BSIG);
-  auto seg_range = [&](const Seg &g, uint64_t e0, uint64_t e1, size_t *lo, size_t *hi) {
-    const uint64_t t0 = eb->tx_start[e0] - bs.tx, t1 = eb->tx_start[e1] - bs.tx;
-    switch (g.kind) {
-      case ALL: *lo = 0; *hi = g.n; break;
-      case EV: *lo = e0 * g.unit; *hi = e1 * g.unit; break;
-      case EV1: *lo = e0 * g.unit; *hi = (e1 + 1) * g.unit; break;
-      case TX: *lo = t0 * g.unit; *hi = t1 * g.unit; break;
-      case TX1: *lo = t0 * g.unit; *hi = (t1 + 1) * g.unit; break;
-      case TXB: *lo = n_tx ? eb->tx_off[t0] - bs.txb : 0; *hi = n_tx ? eb->tx_off[t1] - bs.txb : 0; break;
-      case ITX:
-        *lo = eb->itx_off ? eb->itx_off[e0] - bs.itx : 0;
-        *hi = eb->itx_off ? eb->itx_off[e1] - bs.itx : 0;
-        break;
-      case BSIG:
-        *lo = eb->bsig_off ? eb->bsig_off[e0] - bs.bsig : 0;
-        *hi = eb->bsig_off ? eb->bsig_off[e1] - bs.bsig : 0;
-        break;
-    }
-    *hi = std::min(*hi, g.n);
-    *lo = std::min(*lo, *hi);
-  };
+  const size_t o_r = qf && !text ? plan.add(eb->r_be, n * 32) : 0;
+  const size_t o_cr = qf ? plan.add(eb->creator, n * 4) : 0;
+  const size_t r_end = plan.total;
+  const size_t o_ph = plan.add(eb->parent_hashes, eb->n_parent_hashes * 32);
+  const size_t small_end = plan.total;
+  const size_t o_r_ev = qf || text ? o_r : plan.add(eb->r_be, n * 32, ev, 32);
+  const size_t o_cr_ev = qf ? o_cr : plan.add(eb->creator, n * 4, ev, 4);
+  const size_t o_ix = plan.add(eb->index, n * 8, ev, 8);
+  const size_t o_ts = plan.add(eb->timestamp, n * 8, ev, 8);
+  const size_t o_pk = plan.add(eb->parent_kind, n * 2, ev, 2);
+  const size_t o_pr = plan.add(eb->parent_ref, n * 16, ev, 16);
+  const size_t o_txs = plan.add(eb->tx_start, (n + 1) * 8, ev1, 8);
+  const size_t o_txo = plan.add(eb->tx_off, n_tx ? (n_tx + 1) * 8 : 0, tx1, 8);
+  const size_t o_txb = plan.add(eb->tx_bytes, tx_len, txb, 1, 64);
+  const size_t o_tln = plan.add(eb->tx_list_nil, n, ev, 1);
+  const size_t o_txn = plan.add(eb->tx_nil, n_tx, tx, 1);
+  const size_t o_io = plan.add(eb->itx_off, (n + 1) * 8, ev1, 8);
+  const size_t o_ij = plan.add(eb->itx_json, itx_len, itxb);
+  const size_t o_bo = plan.add(eb->bsig_off, (n + 1) * 8, ev1, 8);
+  const size_t o_bj = plan.add(eb->bsig_json, bsig_len, bsigb);
+  const size_t total = plan.total;
 
   // event chunks of ~kChunk staged bytes (whole 256-event groups, so each
   // chunk's items fill whole words of the accept bitmask)
@@ -516,49 +395,13 @@ int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard
   HIPCHK(hipEventRecord(ctx->S().ev[E_CALL], cs), BV_E_LAUNCH, "event");
   // arrays in bv_host_alloc memory are DMA'd from where they are (no
   // staging copy: what a cgo caller gets by building the wire batch there)
-  std::vector<char> direct(segs.size());
-  for (size_t i = 0; i < segs.size(); i++) direct[i] = segs[i].src && bv_is_pinned(segs[i].src, segs[i].n);
-  auto stage = [&](size_t a0, size_t a1) -> int {
-    for (size_t a = a0; a < a1; a += kChunk) {
-      const size_t z = std::min(a1, a + kChunk);
-      std::vector<CopyPool::Piece> pieces;
-      bool any_direct = false;
-      for (size_t i = 0; i < segs.size(); i++) {
-        const Seg &g = segs[i];
-        const size_t lo = std::max(a, g.off), hi = std::min(z, g.off + g.n);
-        if (g.kind != ALL || !g.src || lo >= hi) continue;
-        if (direct[i]) {
-          any_direct = true;
-          HIPCHK(hipMemcpyAsync(dev + lo, (const uint8_t *)g.src + (lo - g.off), hi - lo, hipMemcpyHostToDevice, cs),
-                 BV_E_LAUNCH, "h2d (pinned caller buffer)");
-        } else {
-          pieces.push_back({pin + lo, (const uint8_t *)g.src + (lo - g.off), hi - lo});
-        }
-      }
-      ctx->pool->copy_many(pieces);
-      if (!any_direct) {
-        HIPCHK(hipMemcpyAsync(dev + a, pin + a, z - a, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-      } else {  // the staged pieces only: the range also holds direct segments
-        for (const CopyPool::Piece &q : pieces) {
-          const size_t o = (uint8_t *)q.dst - pin;
-          HIPCHK(hipMemcpyAsync(dev + o, q.dst, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-        }
-      }
-    }
-    return BV_OK;
-  };
-  rc = stage(0, keys_end);  // the keys: the key tables start once they land
+  plan.mark_direct(bv_is_pinned);
+  rc = bv_stage_range(ctx, plan, 0, keys_end, kChunk);  // the keys: the key tables start once they land
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_KREADY], cs), BV_E_LAUNCH, "event");
-  if (ctx->flags & BV_F_KEY_CACHE) {
-    HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_KREADY], 0), BV_E_LAUNCH, "join");
-    bv_kc_items items;
-    items.n_items = n;  // the shard's creators
-    items.h_item_key = eb->creator;
-    rc = bv_kc_prepare(ctx, eb->n_keys, eb->key_bytes, eb->key_off, d.key_bytes, d.key_off, st, &kc, false, &items);
-    if (rc != BV_OK) return rc;
-  }
-  rc = stage(keys_end, s_end);  // s, pre (or the signature text): s^-1
+  rc = bv_kc_host_step(ctx, eb->key_bytes, eb->key_off, vb, eb->creator, st, &kc);  // (the shard's creators)
+  if (rc != BV_OK) return rc;
+  rc = bv_stage_range(ctx, plan, keys_end, s_end, kChunk);  // s, pre (or the signature text): s^-1
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_SREADY], cs), BV_E_LAUNCH, "event");
   if (text) {  // r, s, pre from the text, ahead of s^-1; the verify stream reads them
@@ -573,13 +416,13 @@ int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard
   rc = bv_run_keys(ctx, &vb, ctx->S().ev[E_KREADY], ctx->S().ev[E_SREADY], kc);
   if (rc != BV_OK) return rc;
   if (qf) {
-    rc = stage(s_end, r_end);  // r, the creators: the key part
+    rc = bv_stage_range(ctx, plan, s_end, r_end, kChunk);  // r, the creators: the key part
     if (rc != BV_OK) return rc;
     HIPCHK(hipEventRecord(ctx->S().ev[E_RREADY], cs), BV_E_LAUNCH, "event");
     rc = pipe.key_part(vst, ctx->S().ev[E_RREADY]);
     if (rc != BV_OK) return rc;
   }
-  rc = stage(r_end, small_end);  // the parent hashes
+  rc = bv_stage_range(ctx, plan, r_end, small_end, kChunk);  // the parent hashes
   if (rc != BV_OK) return rc;
   HIPCHK(hipEventRecord(ctx->S().ev[E_SMALL], cs), BV_E_LAUNCH, "event");
   HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_SMALL], 0), BV_E_LAUNCH, "join");
@@ -604,24 +447,8 @@ int bv_events_launch(bv_ctx *ctx, const bv_event_batch *whole, const bv_ev_shard
   // verified on `vst`
   for (size_t c = 0; c + 1 < cb.size(); c++) {
     const uint64_t e0 = cb[c], e1 = cb[c + 1];
-    std::vector<CopyPool::Piece> pieces;
-    for (size_t i = 0; i < segs.size(); i++) {
-      const Seg &g = segs[i];
-      if (g.kind == ALL || !g.src) continue;
-      size_t lo, hi;
-      seg_range(g, e0, e1, &lo, &hi);
-      if (lo >= hi) continue;
-      if (direct[i])
-        HIPCHK(hipMemcpyAsync(dev + g.off + lo, (const uint8_t *)g.src + lo, hi - lo, hipMemcpyHostToDevice, cs),
-               BV_E_LAUNCH, "h2d (pinned caller buffer)");
-      else
-        pieces.push_back({pin + g.off + lo, (const uint8_t *)g.src + lo, hi - lo});
-    }
-    ctx->pool->copy_many(pieces);  // the rest of the chunk into pinned memory, then its DMA
-    for (const CopyPool::Piece &q : pieces) {
-      const size_t o = (uint8_t *)q.dst - pin;
-      HIPCHK(hipMemcpyAsync(dev + o, pin + o, q.n, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d");
-    }
+    // pinned arrays' slices by DMA from where they lie, the rest into pinned memory, then its DMA
+    if ((rc = bv_stage_slices(ctx, plan, e0, e1)) != BV_OK) return rc;
     hipEvent_t landed = ctx->chunk_ev[c % ctx->chunk_ev.size()];
     HIPCHK(hipEventRecord(landed, cs), BV_E_LAUNCH, "event");
     HIPCHK(hipStreamWaitEvent(st, landed, 0), BV_E_LAUNCH, "join chunk");

@@ -25,6 +25,8 @@
 #include "hostscalar.h"
 #include "geometry.h"
 #include "hostdag.h"
+#include "copypool.h"
+#include "hoststage.h"
 
 #define KS_OK 0  // k_key_decode statuses (verify_core.h)
 
@@ -122,120 +124,6 @@ struct PinnedBuf {
   hipError_t ensure(size_t bytes);
   void release();
 };
-
-// ---------------------------------------------------------------------------
-// host copy pool: parallel memcpy into / out of pinned staging
-// ---------------------------------------------------------------------------
-struct CopyPool {
-  std::vector<std::thread> th;
-  std::mutex mu;
-  std::condition_variable cv, done_cv;
-  std::vector<std::function<void()>> q;
-  size_t pending = 0;
-  bool stop = false;
-  explicit CopyPool(int n) {
-    for (int i = 0; i < n; i++)
-      th.emplace_back([this]() {
-        for (;;) {
-          std::function<void()> f;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [this]() { return stop || !q.empty(); });
-            if (stop && q.empty()) return;
-            f = std::move(q.back());
-            q.pop_back();
-          }
-          f();
-          std::lock_guard<std::mutex> lk(mu);
-          if (--pending == 0) done_cv.notify_all();
-        }
-      });
-  }
-  ~CopyPool() {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      stop = true;
-    }
-    cv.notify_all();
-    for (auto &t : th) t.join();
-  }
-  // fn(lo, hi) over [0, n) in `grain`-sized ranges on the pool and the
-  // caller; returns false if any range returned false.
-  bool parallel_for(uint64_t n, uint64_t grain, const std::function<bool(uint64_t, uint64_t)> &fn) {
-    if (n <= grain || th.empty()) return fn(0, n);
-    const uint64_t parts = (n + grain - 1) / grain;
-    std::atomic<bool> ok{true};
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (uint64_t i = 1; i < parts; i++) {
-        const uint64_t lo = i * grain, hi = std::min(n, lo + grain);
-        q.push_back([&fn, &ok, lo, hi]() {
-          if (!fn(lo, hi)) ok = false;
-        });
-        pending++;
-      }
-    }
-    cv.notify_all();
-    if (!fn(0, std::min(n, grain))) ok = false;
-    std::unique_lock<std::mutex> lk(mu);
-    done_cv.wait(lk, [this]() { return pending == 0; });
-    return ok;
-  }
-  // dst <- src (n bytes); returns when done.  Small copies stay on the caller.
-  void copy(void *dst, const void *src, size_t n) {
-    constexpr size_t kPiece = 2ull << 20;
-    if (n <= kPiece || th.empty()) {
-      if (n) memcpy(dst, src, n);
-      return;
-    }
-    const size_t pieces = (n + kPiece - 1) / kPiece;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (size_t i = 1; i < pieces; i++) {
-        const size_t o = i * kPiece, len = std::min(kPiece, n - o);
-        q.push_back([=]() { memcpy((uint8_t *)dst + o, (const uint8_t *)src + o, len); });
-        pending++;
-      }
-    }
-    cv.notify_all();
-    memcpy(dst, src, std::min(kPiece, n));  // the caller copies the first piece
-    std::unique_lock<std::mutex> lk(mu);
-    done_cv.wait(lk, [this]() { return pending == 0; });
-  }
-  // several copies at once (the pieces of one staging chunk), split into
-  // 1 MB parts spread over the pool; returns when all are done
-  struct Piece {
-    void *dst;
-    const void *src;
-    size_t n;
-  };
-  void copy_many(const std::vector<Piece> &v) {
-    constexpr size_t kPart = 1ull << 20;
-    std::vector<Piece> parts;
-    for (const Piece &p : v)
-      for (size_t o = 0; o < p.n; o += kPart)
-        parts.push_back({(uint8_t *)p.dst + o, (const uint8_t *)p.src + o, std::min(kPart, p.n - o)});
-    if (parts.size() <= 1 || th.empty()) {
-      for (const Piece &p : parts) memcpy(p.dst, p.src, p.n);
-      return;
-    }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (size_t i = 1; i < parts.size(); i++) {
-        const Piece p = parts[i];
-        q.push_back([p]() { memcpy(p.dst, p.src, p.n); });
-        pending++;
-      }
-    }
-    cv.notify_all();
-    memcpy(parts[0].dst, parts[0].src, parts[0].n);
-    std::unique_lock<std::mutex> lk(mu);
-    done_cv.wait(lk, [this]() { return pending == 0; });
-  }
-};
-
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Host entries: a message (bv_verify_batch) or block body (bv_verify_blocks)
 // longer than this is hashed on the host (hostsha.cpp, the SHA extensions)
@@ -400,7 +288,32 @@ struct bv_host_call {
 bool bv_is_pinned(const void *p, size_t n);  // [p, p+n) inside one bv_host_alloc block
 
 int bv_fail(bv_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
+// in a function with a `bv_ctx *ctx` that returns a BV_ code
+#define HIPCHK(expr, code, what)                               \
+  do {                                                         \
+    hipError_t _e = (expr);                                    \
+    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
+  } while (0)
+// the context's pool as the host DAG hasher's parallel-for (hostdag.h)
+inline HostParFor bv_pool_parfor(bv_ctx *ctx) {
+  return [ctx](uint64_t cnt, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn) {
+    ctx->pool->parallel_for(cnt, grain, [&fn](uint64_t lo, uint64_t hi) {
+      fn(lo, hi);
+      return true;
+    });
+  };
+}
 hipStream_t bv_copy_stream(bv_ctx *ctx);   // the device's copy stream (created on first use; nullptr on failure)
+// A staging plan's commands (hoststage.h) between ctx->pin_in and ctx->d_in,
+// in order: pool copies through CopyPool::copy_many (each run of them at
+// once), the DMAs on the copy stream.  bv_stage_range / bv_stage_slices plan
+// layout bytes [a0, a1) / the slices of events [e0, e1) and run them;
+// bv_stage_one_copy gathers every segment, pinned or not, into the staging
+// block and sends the whole layout as one copy.
+int bv_stage_run(bv_ctx *ctx, const std::vector<StageOp> &ops);
+int bv_stage_range(bv_ctx *ctx, const StagePlan &plan, size_t a0, size_t a1, size_t piece);
+int bv_stage_slices(bv_ctx *ctx, const StagePlan &plan, uint64_t e0, uint64_t e1);
+int bv_stage_one_copy(bv_ctx *ctx, const StagePlan &plan);
 // After a failed call: wait until nothing the call may have enqueued on the
 // ctx's streams (and on `st`) is still running, so no slot keeps orphaned
 // kernels that a later call would not wait for.  Returns `rc`.
@@ -489,6 +402,11 @@ struct bv_kc_items {
 int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko, const uint8_t *dkb,
                   const uint64_t *dko, hipStream_t st, bool *use, bool force_build = false,
                   const bv_kc_items *items = nullptr);
+// The key-cache step of a host entry (nothing without BV_F_KEY_CACHE): `st`
+// waits for the keys in HBM (E_KREADY), then bv_kc_prepare over the host keys,
+// their device copy (d's key_bytes / key_off) and the items' keys on the host
+int bv_kc_host_step(bv_ctx *ctx, const uint8_t *hkb, const uint64_t *hko, const bv_batch &d,
+                    const uint32_t *h_item_key, hipStream_t st, bool *kc);
 uint32_t bv_kc_lookup(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko, uint64_t *tabs);
 bool bv_kc_all_cached(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64_t *hko);
 void bv_kc_init(bv_ctx *ctx);     // budget, admission and fault-injection settings (bv_create)

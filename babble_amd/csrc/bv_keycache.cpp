@@ -34,12 +34,6 @@
 
 #include "bv_internal.h"
 
-#define HIPCHK(expr, code, what)                               \
-  do {                                                         \
-    hipError_t _e = (expr);                                    \
-    if (_e != hipSuccess) return bv_fail(ctx, code, what, _e); \
-  } while (0)
-
 namespace {
 // The table, sub-table and prefix-scratch sizes are the context's geometry's
 // (ctx->kc_table_bytes, kc_sub_bytes, kc_pscr_bytes: 805 MB / 1.5 MB / 403 MB
@@ -372,6 +366,16 @@ int bv_kc_prepare(bv_ctx *ctx, uint32_t n_keys, const uint8_t *hkb, const uint64
   HIPCHK(hipMemcpyAsync(ctx->S().kc_tabs.p, tabs, n_keys * 8ull, hipMemcpyHostToDevice, st), BV_E_LAUNCH, "h2d tabs");
   *use = true;
   return BV_OK;
+}
+
+int bv_kc_host_step(bv_ctx *ctx, const uint8_t *hkb, const uint64_t *hko, const bv_batch &d,
+                    const uint32_t *h_item_key, hipStream_t st, bool *kc) {
+  if (!(ctx->flags & BV_F_KEY_CACHE)) return BV_OK;
+  HIPCHK(hipStreamWaitEvent(st, ctx->S().ev[E_KREADY], 0), BV_E_LAUNCH, "join");
+  bv_kc_items items;
+  items.n_items = d.n_items;
+  items.h_item_key = h_item_key;
+  return bv_kc_prepare(ctx, d.n_keys, hkb, hko, d.key_bytes, d.key_off, st, kc, false, &items);
 }
 
 // Host-only lookup for the small-batch path (no device work, no sync): the

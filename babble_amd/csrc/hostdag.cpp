@@ -93,6 +93,70 @@ void dag_hash(const X &x, const bv_event_batch &b, const uint32_t *order, const 
 }
 }  // namespace
 
+const char *bv_check_event_fields(const bv_event_batch *b, CopyPool *pool, bool entry) {
+  const uint64_t n = b->n_events;
+  if (!n) return nullptr;
+  if (!b->creator || !b->index || !b->timestamp || !b->parent_kind || !b->parent_ref || !b->tx_start ||
+      (entry && !b->sig_text && (!b->r_be || !b->s_be)) || !b->key_off)
+    return "null event array";
+  if (entry && b->sig_text) {  // signature text: offsets from 0, monotone
+    if (!b->sig_off || b->sig_off[0] != 0) return "sig_off missing or sig_off[0] != 0";
+    if (!monotone(pool, b->sig_off, n)) return "sig_off not monotone";
+  }
+  if (b->key_off[0] != 0) return "key_off[0] != 0";
+  if (!monotone(nullptr, b->key_off, b->n_keys)) return "key_off not monotone";
+  if (b->key_off[b->n_keys] && !b->key_bytes) return "null key bytes";
+  if (b->tx_start[0] != 0) return "tx_start[0] != 0";
+  const uint64_t n_tx = b->tx_start[n];
+  if (n_tx && !b->tx_off) return "null tx_off";
+  if (n_tx && b->tx_off[0] != 0) return "tx_off[0] != 0";
+  if (!monotone(pool, b->tx_off, n_tx)) return "tx_off not monotone";
+  if (n_tx && b->tx_off[n_tx] && !b->tx_bytes) return "null tx bytes";
+  const uint64_t *offs[2] = {entry ? b->itx_off : nullptr, b->bsig_off};
+  const uint8_t *json[2] = {b->itx_json, b->bsig_json};
+  for (const uint64_t *off : offs)
+    if (off && off[0] != 0) return "fragment offsets must start at 0";
+  for (int f = 0; f < 2; f++)
+    if (offs[f] && offs[f][n] && !json[f]) return "null fragment bytes";
+  for (const uint64_t *off : offs)
+    if (off && !monotone(pool, off, n)) return "fragment offsets not monotone";
+  const auto refs = [b](uint64_t lo, uint64_t hi) {
+    for (uint64_t e = lo; e < hi; e++) {
+      if (b->creator[e] >= b->n_keys || b->tx_start[e] > b->tx_start[e + 1]) return false;
+      for (int p = 0; p < 2; p++) {
+        const uint8_t k = b->parent_kind[2 * e + p];
+        const uint64_t r = b->parent_ref[2 * e + p];
+        if (k > BV_PARENT_EVENT) return false;
+        if (k == BV_PARENT_HASH && (r >= b->n_parent_hashes || !b->parent_hashes)) return false;
+        if (k == BV_PARENT_EVENT && r >= e) return false;  // an in-batch parent precedes its child
+      }
+    }
+    return true;
+  };
+  if (!(pool ? pool->parallel_for(n, 1 << 17, refs) : refs(0, n)))
+    return "bad event reference (creator, tx_start, or a parent not earlier in the batch / out of range)";
+  return nullptr;
+}
+
+void bv_dag_levels(const bv_event_batch &b, std::vector<uint32_t> &order, std::vector<uint32_t> &level_off) {
+  const uint64_t n = b.n_events;
+  std::vector<uint32_t> level(n, 0);
+  uint32_t nl = 1;
+  for (uint64_t e = 0; e < n; e++) {
+    uint32_t l = 0;
+    for (int p = 0; p < 2; p++)
+      if (b.parent_kind[2 * e + p] == BV_PARENT_EVENT) l = std::max(l, level[b.parent_ref[2 * e + p]] + 1);
+    level[e] = l;
+    nl = std::max(nl, l + 1);
+  }
+  level_off.assign(nl + 1, 0);
+  for (uint64_t e = 0; e < n; e++) level_off[level[e] + 1]++;
+  for (uint32_t l = 0; l < nl; l++) level_off[l + 1] += level_off[l];
+  order.resize(n);
+  std::vector<uint32_t> fill(level_off.begin(), level_off.end() - 1);
+  for (uint64_t e = 0; e < n; e++) order[fill[level[e]]++] = (uint32_t)e;
+}
+
 void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
                       const HostParFor &pf, HostDagScratch &w, uint8_t *digests) {
   dag_hash(b, b, order, level_off, n_levels, pf, w, digests);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/babbleverify.h"
+#include "copypool.h"
 
 // fn(lo, hi) over [0, n) in `grain`-sized ranges, possibly on several threads
 using HostParFor = std::function<void(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)> &fn)>;
@@ -23,8 +24,17 @@ struct HostDagScratch {
   std::vector<uint8_t> bodies;
 };
 
-// Levels (level_off, n_levels + 1 entries) and `order` (events sorted by
-// level) as bv_events.cpp computes them; writes the n 32-byte digests.
+// The event fields the serialisers read: nullptr, or what is wrong.  The O(n)
+// scans run on `pool` when there is one.  entry: the rules of a verify entry
+// too (the signature arrays, the InternalTransactions fragment); without it,
+// those of the context-free body helpers, which read neither.
+const char *bv_check_event_fields(const bv_event_batch *b, CopyPool *pool, bool entry);
+
+// DAG levels over in-batch parents (validated: refs point backwards, one
+// pass): level_off gets n_levels + 1 entries, `order` the events by level.
+void bv_dag_levels(const bv_event_batch &b, std::vector<uint32_t> &order, std::vector<uint32_t> &level_off);
+
+// Levels and order as bv_dag_levels gives them; writes the n 32-byte digests.
 void bv_host_dag_hash(const bv_event_batch &b, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
                       const HostParFor &pf, HostDagScratch &w, uint8_t *digests);
 // The same with the InternalTransactions member built from the ITXs' fields

@@ -273,6 +273,39 @@ def test_verify_events_from_pinned_buffers(monkeypatch):
         arena.close()
 
 
+@pytest.mark.gpu
+def test_verify_events_pinned_and_pageable_arrays_in_chunks(monkeypatch):
+    """600 events of 4 creators in three 256-event chunks, tx_bytes and index in
+    bv_host_alloc memory and every other array pageable: per chunk, two slices
+    cross by DMA from where they lie and the rest through the staging block.
+    Digests, statuses and bits equal the all-pageable call's and the oracle's;
+    one signature is corrupted."""
+    import dataclasses
+
+    from babble_amd.verifier import PinnedArena, Verifier
+    from oracle import coracle
+
+    monkeypatch.setenv("BV_EV_CHUNK_MB", "0.001")  # 256-event chunks (read at bv_create)
+    packed, wire = synth.event_fields(600, n_creators=4, seed=29, parents="hash")
+    wire.s_be[333, 7] ^= 0x10
+    packed.s_be[333, 7] ^= 0x10
+    v = Verifier(0)
+    arena = PinnedArena()
+    try:
+        mixed = dataclasses.replace(wire, tx_bytes=arena.copy(wire.tx_bytes),
+                                    index=arena.copy(np.asarray(wire.index, np.int64)))
+        res = v.verify_events(mixed)
+        ref = v.verify_events(wire)
+        h, st, bits = coracle.verify_batch(packed.as_dict())
+        for r in (res, ref):
+            assert np.array_equal(r.msg_hash, h)
+            assert np.array_equal(r.status, st) and np.array_equal(r.accept_bits, bits)
+        assert np.flatnonzero(st != 1).tolist() == [333]
+    finally:
+        v.close()
+        arena.close()
+
+
 # ---------------------------------------------------------------------------
 # The host DAG hasher (babble_amd/csrc/hostdag.cpp + hostsha.cpp): the path
 # bv_verify_events takes for batches with in-batch parents, run here on the

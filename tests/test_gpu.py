@@ -251,6 +251,35 @@ def test_host_entry_single_copy_staging(verifier):
     check_against_oracle(verifier, big)
 
 
+def test_host_entry_pinned_and_pageable_arrays_in_chunks(monkeypatch):
+    """bv_verify_batch over 300 messages of ~1.2 MB in all (two 1 MB message
+    chunks, a layout past the one-copy limit) with s_be and item_key in
+    bv_host_alloc memory and every other array, msg_bytes included, pageable:
+    the pinned arrays cross by DMA from where they lie, their neighbours in
+    the same piece through the staging block one by one.  Equal to the oracle
+    and to the all-pageable call; one signature is corrupted."""
+    import dataclasses
+
+    from babble_amd.verifier import PinnedArena, Verifier
+
+    monkeypatch.setenv("BV_HOST_CHUNK_MB", "1")  # read at bv_create
+    b = synth.events(300, n_creators=8, seed=83, n_tx=16, tx_bytes=180)
+    assert 1.1e6 < b.msg_bytes.nbytes < 1.4e6
+    b.s_be[123, 11] ^= 0x02
+    v = Verifier(device=0)
+    arena = PinnedArena()
+    try:
+        mixed = dataclasses.replace(b, s_be=arena.copy(b.s_be), item_key=arena.copy(b.item_key.astype(np.uint32)))
+        res = check_against_oracle(v, mixed)
+        assert v.timing()["ms_h2d"] > 0  # staged: the bulk pipeline
+        ref = check_against_oracle(v, b)
+        assert np.array_equal(res.status, ref.status) and np.array_equal(res.msg_hash, ref.msg_hash)
+        assert np.flatnonzero(res.status != 1).tolist() == [123]
+    finally:
+        v.close()
+        arena.close()
+
+
 def test_throughput_variants_above_latency_threshold(verifier):
     """Batches of <= 128k items take the verify kernels' latency variants
     (zipped point ops), larger ones the throughput variants: just above the

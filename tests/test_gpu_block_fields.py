@@ -235,6 +235,36 @@ def test_output_forms_write_the_same_values(v0):
         arena.close()
 
 
+def test_pinned_and_pageable_arrays_past_the_one_copy_limit(monkeypatch):
+    """64 blocks x 4 validators with 1.2 MB of tx_bytes (a layout past the 1 MiB
+    one-copy limit; 40 bodies are long enough for the host to hash), tx_bytes in
+    bv_host_alloc memory and every other array pageable: in the block-field
+    phase one array crosses by DMA from where it lies and its neighbours
+    through the staging block one by one.  Equal to the oracle and to the
+    all-pageable call; a tenth of the signatures is corrupted."""
+    import dataclasses
+
+    c = cached("mixed", lambda: BC.signed_case(BC.synth_like_bodies(40, n_tx=16, tx_bytes=1500, seed=3) +
+                                               BC.synth_like_bodies(24, n_tx=9, tx_bytes=1200, seed=4), 4, 4, seed=77,
+                                               corrupt=0.1))
+    assert c.fields.tx_bytes.nbytes > 1_200_000 and c.n_items == 256
+    assert 0 < int((c.oracle()[1] != 1).sum()) < 64
+    monkeypatch.setenv("BV_SMALL", "0")  # (256 items: the bulk pipeline whatever the routing rule says)
+    v = Verifier(0)
+    arena = PinnedArena()
+    try:
+        mixed = dataclasses.replace(c.fields, tx_bytes=arena.copy(c.fields.tx_bytes))
+        res = v.verify_blocks(mixed)
+        assert v.timing()["ms_h2d"] > 0
+        check(c, res, "tx_bytes pinned")
+        ref = v.verify_blocks(c.fields)
+        check(c, ref, "pageable")
+        assert np.array_equal(res.status, ref.status) and np.array_equal(res.msg_hash, ref.msg_hash)
+    finally:
+        v.close()
+        arena.close()
+
+
 def test_validation_errors_then_a_valid_call(v0):
     import ctypes
 

@@ -112,6 +112,44 @@ def test_bulk_route_in_chunks_of_64_events(vbulk, monkeypatch, itx_fields):
         arena.close()
 
 
+def test_chunks_with_one_large_pinned_array(vbulk, monkeypatch):
+    """200 events with at least one block signature each, in chunks of 64 + 64
+    + 64 + 8, with 300 000 bytes of transactions (past the 256 KiB floor) in
+    bv_host_alloc memory and every other array pageable: each chunk's tx_bytes
+    slice crosses by DMA from where it lies, the other slices through the
+    staging block.  Equal to the oracle and to the all-pageable call; every
+    fifth signature is corrupted."""
+    import random
+
+    from babble_amd.verifier import PinnedArena
+
+    def make():
+        rng = random.Random(5)
+        specs = C.cycle_specs(200)
+        for e, s in enumerate(specs):
+            s["txs"] = [bytes(rng.getrandbits(8) for _ in range(750)) for _ in range(2)]
+            if not s["bsigs"]:
+                s["bsigs"] = [C.block_sig(s["c"], 1000 + e, e)]
+        return C.FieldsCase(specs)
+
+    c = cached("big_tx", make)
+    p = c.packed
+    assert p.ev.events.tx_bytes.nbytes == 300_000 and p.n_bsig >= 200 and {0, 1, 4} <= set(c.expected()[0].tolist())
+    monkeypatch.setenv("BV_FIELDS_CHUNK", "64")
+    arena = PinnedArena()
+    try:
+        events = dataclasses.replace(p.ev.events, tx_bytes=arena.copy(p.ev.events.tx_bytes))
+        mixed = dataclasses.replace(p, ev=dataclasses.replace(p.ev, events=events))
+        res = vbulk.verify_events_fields(mixed)
+        assert vbulk.timing()["ms_h2d"] > 0
+        check(c, res, "tx_bytes pinned")
+        ref = vbulk.verify_events_fields(p)
+        check(c, ref, "pageable")
+        same(res, ref)
+    finally:
+        arena.close()
+
+
 @pytest.mark.parametrize("n", [3, 63])
 def test_small_batches_take_the_one_launch_path(n):
     c = cycle_case(n)
