@@ -1635,6 +1635,9 @@ hipError_t verify_g(hipStream_t st, uint64_t n, uint64_t lo, uint64_t hi, const 
   return hipGetLastError();
 }
 
+// kernel K of one key-table geometry, latency or throughput variant
+#define BV_GEOM_KERNEL(K, W, NWIN, lat) ((lat) ? K<W, NWIN, true> : K<W, NWIN, false>)
+
 // kw = 8 / 12: contiguous per-batch tables in key_table; kw = 22 / 18: the
 // key cache (KC / KC18), table base address per batch key in key_tabs.  Any
 // other kw is an error: no kernel runs.
@@ -1644,25 +1647,15 @@ hipError_t verify_q(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t hi
                     uint8_t *status, uint64_t *bits) {
   if (hi <= lo) return hipSuccess;
   const bool lat = lat_variant(n);
-#define BV_LAUNCH_Q(W, NWIN, KT, KTABS)                                                                             \
-  if (lat)                                                                                                       \
-    hipLaunchKernelGGL((k_verify_q<W, NWIN, true>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key,  \
-                       r_be, s_be, pre, kst, u12, KT, KTABS, rg, status, bits);                                  \
-  else                                                                                                           \
-    hipLaunchKernelGGL((k_verify_q<W, NWIN, false>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key,   \
-                       r_be, s_be, pre, kst, u12, KT, KTABS, rg, status, bits);
-  if (kw == 8) {
-    BV_LAUNCH_Q(BV_KW, BV_KNWIN, key_table, nullptr)
-  } else if (kw == 12) {
-    BV_LAUNCH_Q(BV_K12W, BV_K12NWIN, key_table, nullptr)
-  } else if (kw == BV_KCW) {
-    BV_LAUNCH_Q(BV_KCW, BV_KCNWIN, nullptr, key_tabs)
-  } else if (kw == BV_KC18W) {
-    BV_LAUNCH_Q(BV_KC18W, BV_KC18NWIN, nullptr, key_tabs)
-  } else {
-    return hipErrorInvalidValue;  // an unknown geometry never reads a table
-  }
-#undef BV_LAUNCH_Q
+  const bool cached = kw == BV_KCW || kw == BV_KC18W;
+  auto k = kw == 8          ? BV_GEOM_KERNEL(k_verify_q, BV_KW, BV_KNWIN, lat)
+           : kw == 12       ? BV_GEOM_KERNEL(k_verify_q, BV_K12W, BV_K12NWIN, lat)
+           : kw == BV_KCW   ? BV_GEOM_KERNEL(k_verify_q, BV_KCW, BV_KCNWIN, lat)
+           : kw == BV_KC18W ? BV_GEOM_KERNEL(k_verify_q, BV_KC18W, BV_KC18NWIN, lat)
+                            : nullptr;
+  if (!k) return hipErrorInvalidValue;  // an unknown geometry never reads a table
+  hipLaunchKernelGGL(k, grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, r_be, s_be, pre, kst, u12,
+                     cached ? nullptr : key_table, cached ? key_tabs : nullptr, rg, status, bits);
   return hipGetLastError();
 }
 
@@ -1673,25 +1666,15 @@ hipError_t verify_qf(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t h
                      const uint32_t *w, const uint32_t *key_table, const uint64_t *key_tabs, uint32_t *rq) {
   if (hi <= lo) return hipSuccess;
   const bool lat = lat_variant(n);
-#define BV_LAUNCH_QF(W, NWIN, KT, KTABS)                                                                            \
-  if (lat)                                                                                                       \
-    hipLaunchKernelGGL((k_verify_qf<W, NWIN, true>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, \
-                       r_be, s_be, pre, kst, w, KT, KTABS, rq);                                                  \
-  else                                                                                                           \
-    hipLaunchKernelGGL((k_verify_qf<W, NWIN, false>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, \
-                       r_be, s_be, pre, kst, w, KT, KTABS, rq);
-  if (kw == 8) {
-    BV_LAUNCH_QF(BV_KW, BV_KNWIN, key_table, nullptr)
-  } else if (kw == 12) {
-    BV_LAUNCH_QF(BV_K12W, BV_K12NWIN, key_table, nullptr)
-  } else if (kw == BV_KCW) {
-    BV_LAUNCH_QF(BV_KCW, BV_KCNWIN, nullptr, key_tabs)
-  } else if (kw == BV_KC18W) {
-    BV_LAUNCH_QF(BV_KC18W, BV_KC18NWIN, nullptr, key_tabs)
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef BV_LAUNCH_QF
+  const bool cached = kw == BV_KCW || kw == BV_KC18W;
+  auto k = kw == 8          ? BV_GEOM_KERNEL(k_verify_qf, BV_KW, BV_KNWIN, lat)
+           : kw == 12       ? BV_GEOM_KERNEL(k_verify_qf, BV_K12W, BV_K12NWIN, lat)
+           : kw == BV_KCW   ? BV_GEOM_KERNEL(k_verify_qf, BV_KCW, BV_KCNWIN, lat)
+           : kw == BV_KC18W ? BV_GEOM_KERNEL(k_verify_qf, BV_KC18W, BV_KC18NWIN, lat)
+                            : nullptr;
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, r_be, s_be, pre, kst, w,
+                     cached ? nullptr : key_table, cached ? key_tabs : nullptr, rq);
   return hipGetLastError();
 }
 
@@ -1717,23 +1700,15 @@ hipError_t verify_gq(hipStream_t st, int kw, uint64_t n, uint64_t lo, uint64_t h
                      const uint64_t *key_tabs, uint8_t *status, uint64_t *bits) {
   if (hi <= lo) return hipSuccess;
   const bool lat = lat_variant(n);
-#define BV_LAUNCH_GQ(W, NWIN)                                                                                     \
-  if (lat)                                                                                                        \
-    hipLaunchKernelGGL((k_verify_gq<W, NWIN, true>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key,  \
-                       r_be, s_be, pre, kst, item_msg, dig, w, g_table, key_tabs, status, bits);                  \
-  else                                                                                                            \
-    hipLaunchKernelGGL((k_verify_gq<W, NWIN, false>), grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, \
-                       r_be, s_be, pre, kst, item_msg, dig, w, g_table, key_tabs, status, bits);
-  if (kw == BV_KCW) {
-    BV_LAUNCH_GQ(BV_KCW, BV_KCNWIN)
-  } else if (kw == BV_KC18W) {
-    BV_LAUNCH_GQ(BV_KC18W, BV_KC18NWIN)
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef BV_LAUNCH_GQ
+  auto k = kw == BV_KCW     ? BV_GEOM_KERNEL(k_verify_gq, BV_KCW, BV_KCNWIN, lat)
+           : kw == BV_KC18W ? BV_GEOM_KERNEL(k_verify_gq, BV_KC18W, BV_KC18NWIN, lat)
+                            : nullptr;
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, grid1(hi - lo, 256), dim3(256), 0, st, n, lo, hi, item_key, r_be, s_be, pre, kst, item_msg,
+                     dig, w, g_table, key_tabs, status, bits);
   return hipGetLastError();
 }
+#undef BV_GEOM_KERNEL
 
 // Key-cache tables for n keys (decoded affine points kxy, statuses kst) in
 // geometry kw (22: KC, 18: KC18): bases 2^(L k) Q (k < NSUB; L = 11 / 9,

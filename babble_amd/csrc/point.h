@@ -12,6 +12,13 @@
 struct gej {
   fe X, Y, Z;
 };
+// the identity: the flag, over zeroed coordinates
+DEV void pt_set_identity(gej &r, bool &inf) {
+  inf = true;
+  fe_set(r.X, 0);
+  fe_set(r.Y, 0);
+  fe_set(r.Z, 0);
+}
 
 // dbl-2009-l (a = 0): 2M + 5S.  Caller guarantees the input is not the
 // identity; Y == 0 cannot occur on secp256k1 (no 2-torsion, b = 7).
@@ -239,6 +246,13 @@ DEV void gej_add(gej &r, bool &rinf, const gej &b, bool binf) {
 struct gexz {
   fe X, Y, ZZ, ZZZ;
 };
+DEV void pt_set_identity(gexz &r, bool &inf) {
+  inf = true;
+  fe_set(r.X, 0);
+  fe_set(r.Y, 0);
+  fe_set(r.ZZ, 0);
+  fe_set(r.ZZZ, 0);
+}
 
 // r = 2 a (dbl-2008-s-1, a = 0): 6M + 3S.  a is not the identity; Y == 0
 // cannot occur on secp256k1.

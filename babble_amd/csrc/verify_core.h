@@ -197,10 +197,7 @@ __device__ __forceinline__ void coop_bases_one(uint32_t b, const uint32_t *bxy, 
 // returned Z is 1 for d == 0 so it can join a batch inversion.
 template <bool LAT = false>
 DEV void table_point(gej &R, bool &inf, fe &Z, const fe &bx, const fe &by, uint32_t d, int bits) {
-  inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.Z, 0);
+  pt_set_identity(R, inf);
   for (int bit = bits - 1; bit >= 0; bit--) {
     if (!inf) gej_double_sel<LAT>(R, R);
     if ((d >> bit) & 1) gej_add_ge_sel<LAT>(R, inf, bx, by);
@@ -576,23 +573,48 @@ DEV void sinv_block_lane(uint32_t j, uint32_t L, uint32_t B, const uint32_t *tot
   }
 }
 
-// u1 = e s^-1 and the GLV split of u2 = r s^-1 (mod N) for an item that
-// reaches the math (ecdsa.Verify steps 4-6: e = the 256-bit digest,
-// unreduced; w = s^-1 R from k_sinv).
-DEV void item_scalars(uint64_t i, const uint32_t *r_be, const uint32_t *item_msg, const uint32_t *digest_words,
-                      const uint32_t *w_in, uint32_t u1[8], uint32_t k1[4], uint32_t k2[4], uint32_t &signs) {
-  sc w, e, r, a, b;
+// The scalars of an item that reaches the math (ecdsa.Verify steps 4-6).
+// w = s^-1 R of item i, as k_sinv stored it
+DEV void sc_load_w(sc &w, const uint32_t *w_in, uint64_t i) {
   const uint4 *q = (const uint4 *)(w_in + 8 * i);
   const uint4 x = q[0], y = q[1];
   w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
   w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
+}
+// u1 = e s^-1 mod N (e = the 256-bit digest, unreduced: e < 2^256 = R, w < N)
+DEV void u1_from(const sc &e, const sc &w, uint32_t u[8]) {
+  sc a;
+  sc_mont(a, e, w);
+#pragma unroll
+  for (int k = 0; k < 8; k++) u[k] = a.v[k];
+}
+DEV void u1_of(uint64_t i, const uint32_t *item_msg, const uint32_t *digest_words, const sc &w, uint32_t u[8]) {
+  sc e;
+  sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
+  u1_from(e, w, u);
+}
+// the GLV split of u2 = r s^-1 mod N
+DEV void u2_split_from(const sc &r, const sc &w, uint32_t k1[4], uint32_t k2[4], uint32_t &signs) {
+  sc b;
+  sc_mont(b, r, w);
+  glv_split(k1, k2, signs, b);
+}
+DEV void u2_split_of(uint64_t i, const uint32_t *r_be, const sc &w, uint32_t k1[4], uint32_t k2[4], uint32_t &signs) {
+  sc r;
+  sc_load_be_words(r, r_be + 8 * i);
+  u2_split_from(r, w, k1, k2, signs);
+}
+// both, from the batch arrays; the three loads stand in front of the two
+// products (through u1_of / u2_split_of the non-split k_verify_g needs 136
+// VGPRs instead of 123 and loses its fourth wave per SIMD)
+DEV void item_scalars(uint64_t i, const uint32_t *r_be, const uint32_t *item_msg, const uint32_t *digest_words,
+                      const uint32_t *w_in, uint32_t u1[8], uint32_t k1[4], uint32_t k2[4], uint32_t &signs) {
+  sc w, e, r;
+  sc_load_w(w, w_in, i);
   sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
   sc_load_be_words(r, r_be + 8 * i);
-  sc_mont(a, e, w);  // e * s^-1 mod N  (e < 2^256 = R, w < N)
-  sc_mont(b, r, w);  // r * s^-1 mod N
-#pragma unroll
-  for (int k = 0; k < 8; k++) u1[k] = a.v[k];
-  glv_split(k1, k2, signs, b);
+  u1_from(e, w, u1);
+  u2_split_from(r, w, k1, k2, signs);
 }
 
 // Key-cache batches with a few keys that have no table yet (bv_kc_prepare's
@@ -754,6 +776,17 @@ DEV bool defer_uniform(bool chk) {
 #else
   return chk;
 #endif
+}
+// after an item's last loop: true for the lane that goes round again, checked
+template <bool DEFER>
+DEV bool defer_redo(const gexz &R, bool inf, bool chk) {
+  if constexpr (DEFER) {
+    if (!chk) {
+      const bool bad = defer_flagged(R, inf);
+      if (defer_any_flagged(bad)) return bad;
+    }
+  }
+  return false;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -923,13 +956,8 @@ DEV void g_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8], bool 
     return;
   }
   for (int j = 0; j < NWIN; j++) {
-    uint32_t d = (u[0] & ((1u << W) - 1u)) + carry;
-#pragma unroll
-    for (int c = 0; c < 7; c++) u[c] = (u[c] >> W) | (u[c + 1] << (32 - W));
-    u[7] >>= W;
-    carry = d > ENT ? 1u : 0u;
-    const bool dneg = carry != 0;
-    if (dneg) d = (1u << W) - d;  // |d - 2^W|, 0 when d == 2^W
+    bool dneg;
+    const uint32_t d = next_digit<W, 8, true>(u, carry, dneg);
     // loaded unconditionally (d == 0 reads the window's slot 0, a valid
     // entry that is then not added): no per-lane branch around the lookup
     const uint32_t *e = tab + ((uint64_t)j * ENT + d) * BV_ENTRY_U32;
@@ -954,6 +982,12 @@ DEV void load_k(uint32_t k1[4], uint32_t k2[4], uint32_t &signs, const uint32_t 
   k1[0] = a.x; k1[1] = a.y; k1[2] = a.z; k1[3] = a.w;
   k2[0] = b.x; k2[1] = b.y; k2[2] = b.z; k2[3] = b.w;
   signs = c.x;
+}
+DEV void store_k(uint32_t *u12, uint64_t i, const uint32_t k1[4], const uint32_t k2[4], uint32_t signs) {
+  uint4 *q = (uint4 *)(u12 + (uint64_t)BV_U_STRIDE * i);
+  q[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
+  q[1] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
+  q[2] = make_uint4(signs, 0u, 0u, 0u);
 }
 
 // Partial point R_G = u1 G (XYZZ), kept in HBM between k_verify_g and
@@ -989,19 +1023,11 @@ DEV void rg_load(const uint32_t *rg, uint64_t n, uint64_t i, gexz &R, bool &inf)
 // (the digest's product).  Items whose s is unusable get a split of a
 // dummy w that k_verify_q never reads (it classifies first).
 DEV void glv_split_item(uint64_t i, const uint32_t *r_be, const uint32_t *w_in, uint32_t *u12) {
-  sc w, r, b;
-  const uint4 *q = (const uint4 *)(w_in + 8 * i);
-  const uint4 x = q[0], y = q[1];
-  w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-  w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-  sc_load_be_words(r, r_be + 8 * i);
-  sc_mont(b, r, w);  // r * s^-1 mod N
+  sc w;
   uint32_t k1[4], k2[4], signs;
-  glv_split(k1, k2, signs, b);
-  uint4 *o = (uint4 *)(u12 + (uint64_t)BV_U_STRIDE * i);
-  o[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
-  o[1] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
-  o[2] = make_uint4(signs, 0u, 0u, 0u);
+  sc_load_w(w, w_in, i);
+  u2_split_of(i, r_be, w, k1, k2, signs);
+  store_k(u12, i, k1, k2, signs);
 }
 
 // SPLIT: u12 already holds the GLV split (k_glv_split); else it is formed
@@ -1018,45 +1044,26 @@ DEV void verify_item_g(uint64_t i, uint64_t n, const uint32_t *item_key, const u
     chk = defer_uniform(chk);
     uint32_t u[8];
     if (SPLIT) {
-      sc w, e, a;
-      const uint4 *q = (const uint4 *)(w_in + 8 * i);
-      const uint4 x = q[0], y = q[1];
-      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-      sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
-      sc_mont(a, e, w);  // e * s^-1 mod N
-#pragma unroll
-      for (int k = 0; k < 8; k++) u[k] = a.v[k];
+      sc w;
+      sc_load_w(w, w_in, i);
+      u1_of(i, item_msg, digest_words, w, u);
     } else {
       uint32_t k1[4], k2[4], signs;
       item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
-      uint4 *q = (uint4 *)(u12 + (uint64_t)BV_U_STRIDE * i);
-      q[0] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
-      q[1] = make_uint4(k2[0], k2[1], k2[2], k2[3]);
-      q[2] = make_uint4(signs, 0u, 0u, 0u);
+      store_k(u12, i, k1, k2, signs);
     }
     gexz R;
-    bool inf = true;
-    fe_set(R.X, 0);
-    fe_set(R.Y, 0);
-    fe_set(R.ZZ, 0);
-    fe_set(R.ZZZ, 0);
+    bool inf;
+    pt_set_identity(R, inf);
     bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum
     g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER, y_alt(LAT, 1)>(R, inf, g_table, u, chk, &yn);
     y_true(R, yn);  // R_G is stored with its true Y
-    if constexpr (DEFER) {
-      // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC).  On this
-      // chain it cannot happen (the partial sums
-      // of the signed digits are smaller than the next entry's scalar and the
-      // total is u1 in (0, N)); the test stays, so that the stored R_G, from
-      // which k_verify_q's chain starts, provably has ZZ != 0.
-      if (!chk) {
-        const bool bad = defer_flagged(R, inf);
-        if (defer_any_flagged(bad)) {
-          if (bad) continue;
-        }
-      }
-    }
+    // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC).  On this
+    // chain it cannot happen (the partial sums
+    // of the signed digits are smaller than the next entry's scalar and the
+    // total is u1 in (0, N)); the test stays, so that the stored R_G, from
+    // which k_verify_q's chain starts, provably has ZZ != 0.
+    if (defer_redo<DEFER>(R, inf, chk)) continue;
     rg_store(rg, n, i, R, inf);
     return;
   }
@@ -1130,19 +1137,8 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
   constexpr bool fold = !LAT;  // the latency variants keep negating the accumulator around the half
   if (!fold && neg) fe_neg(R.Y, R.Y);
   for (int j = 0; j < NWIN; j++) {
-    uint32_t d = (k[0] & ((1u << W) - 1u)) + carry;
-    k[0] = (k[0] >> W) | (k[1] << (32 - W));
-    k[1] = (k[1] >> W) | (k[2] << (32 - W));
-    k[2] = (k[2] >> W) | (k[3] << (32 - W));
-    k[3] >>= W;
-    bool dneg = false;
-    if (SIGNED) {
-      carry = d > ENT ? 1u : 0u;
-      if (carry) {
-        d = (1u << W) - d;  // |d - 2^W|, 0 when d == 2^W
-        dneg = true;
-      }
-    }
+    bool dneg;
+    const uint32_t d = next_digit<W, 4, SIGNED>(k, carry, dneg);
     const uint32_t *e = tab + ((uint64_t)j * ENT + d) * BV_ENTRY_U32;  // d == 0: a valid, unused slot
     fe x, y;
     fe_load4(x, e);
@@ -1164,27 +1160,63 @@ DEV void key_table_add(PT &R, bool &inf, const uint32_t *tab, uint32_t k[4], boo
   if (!fold && neg) fe_neg(R.Y, R.Y);
 }
 
-// Phase 2: R = R_G + k1 Q + k2 phi(Q) with the key's two half-tables;
-// final check -> status.
-// key_tabs != null (key cache): per-batch-key table base addresses, else
-// the tables are contiguous in key_table (per-batch K8 / K12 build).
-template <int W, int NWIN, bool LAT = false>
-DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, const uint32_t *r_be,
-                          const uint32_t *s_be, const uint8_t *pre, const uint8_t *kstatus, const uint32_t *u12,
-                          const uint32_t *key_table, const uint64_t *key_tabs, const uint32_t *rg) {
-  constexpr bool SIGNED = W != BV_KW;
-  constexpr bool KC = BV_W_IS_CACHED(W);  // one stored half, phi(T) formed per lookup
-  constexpr uint64_t half =
+// A key's table of W-bit windows: SIGNED digits for every geometry but K8;
+// KC (the cached geometries): one stored half, phi(T) formed per lookup;
+// `half`: the words of one stored half.
+template <int W, int NWIN>
+struct key_geom {
+  static constexpr bool SIGNED = W != BV_KW;
+  static constexpr bool KC = BV_W_IS_CACHED(W);
+  static constexpr uint64_t half =
       SIGNED ? ((uint64_t)NWIN * (1ull << (W - 1)) + 1) * BV_ENTRY_U32 : (uint64_t)NWIN * (1ull << W) * BV_ENTRY_U32;
   static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
   static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
   static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
+};
+// The table of item i's key.  key_tabs != null (key cache): per-batch-key
+// table base addresses, null for a key without a table; else the tables are
+// contiguous in key_table (per-batch K8 / K12 build).
+template <int W, int NWIN>
+DEV const uint32_t *key_table_of(const uint32_t *item_key, uint64_t i, const uint32_t *key_table,
+                                 const uint64_t *key_tabs) {
+  using G = key_geom<W, NWIN>;
+  return key_tabs ? (const uint32_t *)key_tabs[item_key[i]]
+                  : key_table + (uint64_t)item_key[i] * (G::KC ? 1 : 2) * G::half;
+}
+
+// R += k1 T + k2 phi(T) over the key's table (the second stored half, or
+// phi of the first when KC).  One loop body for both GLV halves (one inlined
+// copy of the point addition: smaller code, fewer live registers than two
+// calls).  from_inf_first: R enters the first half as the identity;
+// last_second: only X and ZZ are read after the second half (key_table_add).
+template <int W, int NWIN, bool LAT, bool DEFER>
+DEV void key_halves_add(gexz &R, bool &inf, const uint32_t *tab, const uint32_t k1[4], const uint32_t k2[4],
+                        uint32_t signs, bool from_inf_first, bool last_second, bool chk, bool *yn) {
+  using G = key_geom<W, NWIN>;
+  constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
+  lane_park park;
+  if (PARK) park.put(k2);
+#pragma unroll 1
+  for (int h = 0; h < 2; h++) {
+    uint32_t kk[4];
+    glv_half<PARK>(kk, h, k1, k2, park);
+    key_table_add<W, NWIN, G::SIGNED, LAT, gexz, DEFER, y_alt(LAT, 2)>(
+        R, inf, tab + (h && !G::KC ? G::half : 0), kk, (signs >> h) & 1u, G::KC && h, from_inf_first && h == 0,
+        last_second && h == 1, chk, yn);
+  }
+}
+
+// Phase 2: R = R_G + k1 Q + k2 phi(Q) with the key's two half-tables;
+// final check -> status.
+template <int W, int NWIN, bool LAT = false>
+DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, const uint32_t *r_be,
+                          const uint32_t *s_be, const uint8_t *pre, const uint8_t *kstatus, const uint32_t *u12,
+                          const uint32_t *key_table, const uint64_t *key_tabs, const uint32_t *rg) {
   constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 2) != 0 && !LAT;
   fe r;
   const uint8_t st = classify_item(i, item_key, r_be, s_be, pre, kstatus, r);
   if (st != 0xFF) return st;
-  const uint32_t *tab = key_tabs ? (const uint32_t *)key_tabs[item_key[i]]
-                                 : key_table + (uint64_t)item_key[i] * (KC ? 1 : 2) * half;
+  const uint32_t *tab = key_table_of<W, NWIN>(item_key, i, key_table, key_tabs);
   if (!tab) return BV_DEFERRED;  // key cache, partial batch: no table for this key
   for (bool chk = false;; chk = true) {  // a second pass only for a flagged item (BV_DEFER_EXC)
     chk = defer_uniform(chk);
@@ -1193,32 +1225,13 @@ DEV uint8_t verify_item_q(uint64_t i, uint64_t n, const uint32_t *item_key, cons
     gexz R;
     bool inf;
     rg_load(rg, n, i, R, inf);
-    // One loop body for both GLV halves (one inlined copy of the point
-    // addition: smaller code, fewer live registers than two calls).
-    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-    lane_park park;
-    if (PARK) park.put(k2);
     bool yn = false;  // BV_Y_ALT: R_G comes with its true Y; final_check reads no Y
-#pragma unroll 1
-    for (int h = 0; h < 2; h++) {
-      uint32_t kk[4];
-      glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab + (h && !KC ? half : 0), kk,
-                                                                      (signs >> h) & 1u, KC && h, false, h == 1, chk,
-                                                                      &yn);
-    }
-    if constexpr (DEFER) {
-      // ZZ == 0 <=> some step of either half had P == 0 (the lemma at
-      // BV_DEFER_EXC; R_G entered with ZZ != 0: k_verify_g tested it).  The
-      // flagged item starts again from R_G and u12 in memory, every step
-      // checked.
-      if (!chk) {
-        const bool bad = defer_flagged(R, inf);
-        if (defer_any_flagged(bad)) {
-          if (bad) continue;
-        }
-      }
-    }
+    key_halves_add<W, NWIN, LAT, DEFER>(R, inf, tab, k1, k2, signs, false, true, chk, &yn);
+    // ZZ == 0 <=> some step of either half had P == 0 (the lemma at
+    // BV_DEFER_EXC; R_G entered with ZZ != 0: k_verify_g tested it).  The
+    // flagged item starts again from R_G and u12 in memory, every step
+    // checked.
+    if (defer_redo<DEFER>(R, inf, chk)) continue;
     fe_load_be_words(r, r_be + 8 * i);  // reloaded: not kept live through the loop
     return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
@@ -1234,18 +1247,10 @@ template <int W, int NWIN, bool LAT = false>
 DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, const uint32_t *r_be,
                             const uint32_t *s_be, const uint8_t *pre, const uint8_t *kstatus, const uint32_t *w_in,
                             const uint32_t *key_table, const uint64_t *key_tabs, uint32_t *rq) {
-  constexpr bool SIGNED = W != BV_KW;
-  constexpr bool KC = BV_W_IS_CACHED(W);
-  constexpr uint64_t half =
-      SIGNED ? ((uint64_t)NWIN * (1ull << (W - 1)) + 1) * BV_ENTRY_U32 : (uint64_t)NWIN * (1ull << W) * BV_ENTRY_U32;
-  static_assert(W != BV_K12W || half == BV_K12HALF_U32, "K12 geometry");
-  static_assert(W != BV_KCW || half == BV_KCHALF_U32, "KC geometry");
-  static_assert(W != BV_KC18W || half == BV_KC18HALF_U32, "KC18 geometry");
   constexpr bool DEFER = BV_DEFER_EXC != 0 && (BV_LOOKUP_PIPE & 2) != 0 && !LAT;
   fe r;
   if (classify_item(i, item_key, r_be, s_be, pre, kstatus, r) != 0xFF) return;
-  const uint32_t *tab = key_tabs ? (const uint32_t *)key_tabs[item_key[i]]
-                                 : key_table + (uint64_t)item_key[i] * (KC ? 1 : 2) * half;
+  const uint32_t *tab = key_table_of<W, NWIN>(item_key, i, key_table, key_tabs);
   if (!tab) {  // key cache, partial batch: k_verify_gf leaves the item BV_DEFERRED
     rq[(uint64_t)32 * n + i] = 2u;
     return;
@@ -1254,46 +1259,21 @@ DEV void verify_item_qfirst(uint64_t i, uint64_t n, const uint32_t *item_key, co
     chk = defer_uniform(chk);
     uint32_t k1[4], k2[4], signs;
     {
-      sc w, rs, b;
-      const uint4 *q = (const uint4 *)(w_in + 8 * i);
-      const uint4 x = q[0], y = q[1];
-      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-      sc_load_be_words(rs, r_be + 8 * i);
-      sc_mont(b, rs, w);  // r * s^-1 mod N
-      glv_split(k1, k2, signs, b);
+      sc w;
+      sc_load_w(w, w_in, i);
+      u2_split_of(i, r_be, w, k1, k2, signs);
     }
     gexz R;
-    bool inf = true;
-    fe_set(R.X, 0);
-    fe_set(R.Y, 0);
-    fe_set(R.ZZ, 0);
-    fe_set(R.ZZZ, 0);
-    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-    lane_park park;
-    if (PARK) park.put(k2);
+    bool inf;
+    pt_set_identity(R, inf);
     bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum
-#pragma unroll 1
-    for (int h = 0; h < 2; h++) {
-      uint32_t kk[4];
-      glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, SIGNED, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab + (h && !KC ? half : 0), kk,
-                                                                      (signs >> h) & 1u, KC && h, h == 0, false, chk,
-                                                                      &yn);
-    }
+    key_halves_add<W, NWIN, LAT, DEFER>(R, inf, tab, k1, k2, signs, true, false, chk, &yn);
     y_true(R, yn);  // R_Q is stored with its true Y
-    if constexpr (DEFER) {
-      // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC; the
-      // chain starts from the identity).  The flagged item starts again from
-      // w_in, every step checked, so the stored R_Q has ZZ != 0 when
-      // k_verify_gf continues from it.
-      if (!chk) {
-        const bool bad = defer_flagged(R, inf);
-        if (defer_any_flagged(bad)) {
-          if (bad) continue;
-        }
-      }
-    }
+    // ZZ == 0 <=> some step had P == 0 (the lemma at BV_DEFER_EXC; the
+    // chain starts from the identity).  The flagged item starts again from
+    // w_in, every step checked, so the stored R_Q has ZZ != 0 when
+    // k_verify_gf continues from it.
+    if (defer_redo<DEFER>(R, inf, chk)) continue;
     rg_store(rq, n, i, R, inf);
     return;
   }
@@ -1313,15 +1293,9 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
     chk = defer_uniform(chk);
     uint32_t u[8];
     {
-      sc w, e, a;
-      const uint4 *q = (const uint4 *)(w_in + 8 * i);
-      const uint4 x = q[0], y = q[1];
-      w.v[0] = x.x; w.v[1] = x.y; w.v[2] = x.z; w.v[3] = x.w;
-      w.v[4] = y.x; w.v[5] = y.y; w.v[6] = y.z; w.v[7] = y.w;
-      sc_load_be_words(e, digest_words + 8 * (uint64_t)item_msg[i]);
-      sc_mont(a, e, w);  // e * s^-1 mod N  (e < 2^256 = R, w < N)
-#pragma unroll
-      for (int k = 0; k < 8; k++) u[k] = a.v[k];
+      sc w;
+      sc_load_w(w, w_in, i);
+      u1_of(i, item_msg, digest_words, w, u);
     }
     gexz R;
     bool inf;
@@ -1329,18 +1303,11 @@ DEV uint8_t verify_item_gfinish(uint64_t i, uint64_t n, const uint32_t *item_key
     // BV_Y_ALT is not applied here: the alternating form raised k_verify_gf's
     // scratch (44 -> 48 B), and this kernel waits for PCIe, not for its VALU
     g_table_add<BV_GW, BV_GNWIN, LAT, gexz, false, true, DEFER>(R, inf, g_table, u, chk);
-    if constexpr (DEFER) {
-      // ZZ == 0 <=> some G step had P == 0 (the lemma at BV_DEFER_EXC; R_Q
-      // entered with ZZ != 0: k_verify_qf tested it).  G entries added to
-      // R_Q can meet R_Q itself or its opposite, so here the test does fire:
-      // the flagged item starts again from R_Q in memory, every step checked.
-      if (!chk) {
-        const bool bad = defer_flagged(R, inf);
-        if (defer_any_flagged(bad)) {
-          if (bad) continue;
-        }
-      }
-    }
+    // ZZ == 0 <=> some G step had P == 0 (the lemma at BV_DEFER_EXC; R_Q
+    // entered with ZZ != 0: k_verify_qf tested it).  G entries added to
+    // R_Q can meet R_Q itself or its opposite, so here the test does fire:
+    // the flagged item starts again from R_Q in memory, every step checked.
+    if (defer_redo<DEFER>(R, inf, chk)) continue;
     fe_load_be_words(r, r_be + 8 * i);
     return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
@@ -1369,35 +1336,16 @@ DEV uint8_t verify_item_gq_kc(uint64_t i, const uint32_t *item_key, const uint32
     uint32_t u[8], k1[4], k2[4], signs;
     item_scalars(i, r_be, item_msg, digest_words, w_in, u, k1, k2, signs);
     gexz R;
-    bool inf = true;
-    fe_set(R.X, 0);
-    fe_set(R.Y, 0);
-    fe_set(R.ZZ, 0);
-    fe_set(R.ZZZ, 0);
+    bool inf;
+    pt_set_identity(R, inf);
     bool yn = false;  // BV_Y_ALT: R holds the opposite of the sum; final_check reads no Y
     g_table_add<BV_GW, BV_GNWIN, LAT, gexz, true, false, DEFER, y_alt(LAT, 1)>(R, inf, g_table, u, chk, &yn);
     if (!y_alt(LAT, 2)) y_true(R, yn);
-    constexpr bool PARK = (BV_LOOKUP_PIPE & 2) && !LAT;
-    lane_park park;
-    if (PARK) park.put(k2);
-#pragma unroll 1
-    for (int h = 0; h < 2; h++) {
-      uint32_t kk[4];
-      glv_half<PARK>(kk, h, k1, k2, park);
-      key_table_add<W, NWIN, true, LAT, gexz, DEFER, y_alt(LAT, 2)>(R, inf, tab, kk, (signs >> h) & 1u, h != 0, false,
-                                                                    h == 1, chk, &yn);
-    }
-    if constexpr (DEFER) {
-      // ZZ == 0 <=> some step of the G chain or of either half had P == 0
-      // (the lemma at BV_DEFER_EXC; the item's one chain starts from the
-      // identity).  The flagged item starts again, every step checked.
-      if (!chk) {
-        const bool bad = defer_flagged(R, inf);
-        if (defer_any_flagged(bad)) {
-          if (bad) continue;
-        }
-      }
-    }
+    key_halves_add<W, NWIN, LAT, DEFER>(R, inf, tab, k1, k2, signs, false, true, chk, &yn);
+    // ZZ == 0 <=> some step of the G chain or of either half had P == 0
+    // (the lemma at BV_DEFER_EXC; the item's one chain starts from the
+    // identity).  The flagged item starts again, every step checked.
+    if (defer_redo<DEFER>(R, inf, chk)) continue;
     fe_load_be_words(r, r_be + 8 * i);
     return final_check(R, inf, r) ? BV_ACCEPT : BV_REJECT;
   }
@@ -1425,10 +1373,8 @@ DEV uint8_t verify_item_generic(uint64_t i, const uint32_t *item_key, const uint
   if (signs & 1u) fe_neg(q1y, q1y);
   if (signs & 2u) fe_neg(q2y, q2y);
   gej R;
-  bool inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.Z, 0);
+  bool inf;
+  pt_set_identity(R, inf);
   for (int bit = 127; bit >= 0; bit--) {
     if (!inf) gej_double_sel<LAT>(R, R);
     if ((k1[bit >> 5] >> (bit & 31)) & 1u) gej_add_ge_sel<LAT>(R, inf, q1x, q1y);
@@ -1456,12 +1402,8 @@ DEV void sinv_one(sc &w, const sc &s) {
 // u1 = e w and the GLV split of u2 = r w (item_scalars over values)
 DEV void scalars_from(const sc &w, const sc &e, const sc &r, uint32_t u1[8], uint32_t k1[4], uint32_t k2[4],
                       uint32_t &signs) {
-  sc a, b;
-  sc_mont(a, e, w);
-  sc_mont(b, r, w);
-#pragma unroll
-  for (int k = 0; k < 8; k++) u1[k] = a.v[k];
-  glv_split(k1, k2, signs, b);
+  u1_from(e, w, u1);
+  u2_split_from(r, w, k1, k2, signs);
 }
 
 // g_table_add over windows [j0, j1) only: the signed recoding runs over
@@ -1472,13 +1414,8 @@ DEV void g_table_add_range(PT &R, bool &inf, const uint32_t *tab, uint32_t u[8],
   constexpr uint32_t ENT = 1u << (W - 1);
   uint32_t carry = 0;
   for (int j = 0; j < NWIN; j++) {
-    uint32_t d = (u[0] & ((1u << W) - 1u)) + carry;
-#pragma unroll
-    for (int c = 0; c < 7; c++) u[c] = (u[c] >> W) | (u[c + 1] << (32 - W));
-    u[7] >>= W;
-    carry = d > ENT ? 1u : 0u;
-    const bool dneg = carry != 0;
-    if (dneg) d = (1u << W) - d;
+    bool dneg;
+    const uint32_t d = next_digit<W, 8, true>(u, carry, dneg);
     if (j < j0 || j >= j1) continue;
     const uint32_t *e = tab + ((uint64_t)j * ENT + d) * BV_ENTRY_U32;
     fe x, y;
@@ -1521,10 +1458,7 @@ DEV void naf_mul(gej &R, bool &inf, const fe &px, const fe &py, const uint32_t k
   }
   fe ny;
   fe_neg(ny, py);
-  inf = true;
-  fe_set(R.X, 0);
-  fe_set(R.Y, 0);
-  fe_set(R.Z, 0);
+  pt_set_identity(R, inf);
   for (int bit = 129; bit >= 0; bit--) {
     if (!inf) gej_double_sel<LAT>(R, R);
     const uint32_t p = (pos[bit >> 5] >> (bit & 31)) & 1u, n = (neg[bit >> 5] >> (bit & 31)) & 1u;
@@ -1544,15 +1478,8 @@ template <int W, int NW>
 DEV uint64_t table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, uint32_t u[NW], int j, bool neg, bool phi) {
   constexpr uint32_t ENT = 1u << (W - 1);
   uint32_t carry = 0, d = 0;
-  for (int w = 0; w <= j; w++) {
-    d = (u[0] & ((1u << W) - 1u)) + carry;
-#pragma unroll
-    for (int c = 0; c < NW - 1; c++) u[c] = (u[c] >> W) | (u[c + 1] << (32 - W));
-    u[NW - 1] >>= W;
-    carry = d > ENT ? 1u : 0u;
-  }
-  const bool dneg = carry != 0;
-  if (dneg) d = (1u << W) - d;  // |d - 2^W|, 0 when d == 2^W
+  bool dneg = false;
+  for (int w = 0; w <= j; w++) d = next_digit<W, NW, true>(u, carry, dneg);  // the last digit is window j's
   zero = d == 0;
   const uint64_t slot = (uint64_t)j * ENT + d;
   const uint32_t *e = tab + slot * BV_ENTRY_U32;  // d == 0: a valid, unused slot
@@ -1589,8 +1516,7 @@ template <int KW, int KNWIN>
 DEV uint64_t small_table_leaf(fe &x, fe &y, bool &zero, const uint32_t *tab, const uint32_t k12[8], uint32_t signs,
                               uint32_t q) {
   static_assert(BV_W_IS_CACHED(KW) && KW * KNWIN >= 129 && KW * (KNWIN - 1) < 128, "a cached geometry over a GLV half");
-  static_assert(((uint64_t)KNWIN * (1ull << (KW - 1)) + 1) * BV_ENTRY_U32 ==
-                    (KW == BV_KCW ? BV_KCHALF_U32 : BV_KC18HALF_U32),
+  static_assert(key_geom<KW, KNWIN>::half == (KW == BV_KCW ? BV_KCHALF_U32 : BV_KC18HALF_U32),
                 "the stored half of the cached geometry");
   const uint32_t h = q / KNWIN;
   uint32_t kk[4];
