@@ -8,7 +8,7 @@ device handle (verifier) and a mirror of the reference's Go interface
 """
 from .native import ACCEPT, REF_PANIC, REJECT, REJECT_ERR, BvError, ReferencePanic  # noqa: F401
 
-from .verifier import Group, Verifier, plan_event_shards  # noqa: F401
+from .verifier import Group, Verifier, plan_block_shards, plan_event_shards  # noqa: F401
 
 __all__ = ["ACCEPT", "REJECT", "REJECT_ERR", "REF_PANIC", "BvError", "ReferencePanic", "Group", "Verifier",
-           "plan_event_shards"]
+           "plan_block_shards", "plan_event_shards"]

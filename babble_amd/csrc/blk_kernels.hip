@@ -1,6 +1,9 @@
 // blk_kernels.hip — gfx950 kernels of bv_verify_blocks (bv_blocks.cpp drives
 // them): BlockBody JSON built from the blocks' fields and hashed
-// as it is built, and CheckBlock's tally per block.  A translation unit of its
+// as it is built, and CheckBlock's tally per block; for a shard of
+// bv_group_verify_blocks, the same over the shard's slices (k_blk_body_hash_rb)
+// and its items' block indices less its first block (k_blk_item_rebase).  A
+// translation unit of its
 // own, so that the code object of kernels.hip (the verify kernels) is the
 // same with and without this entry.
 #include <hip/hip_runtime.h>
@@ -40,6 +43,44 @@ __global__ void __launch_bounds__(NT) k_blk_body_hash(bv_block_batch b, uint64_t
   uint4 *dst = (uint4 *)(dig + 8 * k);
   dst[0] = make_uint4(be[0], be[1], be[2], be[3]);
   dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
+}
+
+// The same over a shard (bv_group_verify_blocks): `b` holds the slices of
+// blocks [bs.blk, ...) of a larger batch, [b0, b1) are that batch's block
+// indices, and `dig` and `long_idx` are the shard's: block k's digest is row
+// k - bs.blk, which is also how the long blocks are listed (k_put_digests
+// writes their rows of the same array).
+template <int NT>
+__global__ void __launch_bounds__(NT) k_blk_body_hash_rb(bv_block_batch b, uint64_t b0, uint64_t b1,
+                                                         const uint64_t *__restrict__ long_idx, uint64_t n_long,
+                                                         BlkBases bs, uint32_t *__restrict__ dig) {
+  __shared__ uint32_t rows[NT * BLK_ROW];
+  const uint64_t k = b0 + (uint64_t)blockIdx.x * NT + threadIdx.x;
+  if (k >= b1) return;  // no barriers below
+  const uint64_t row = k - bs.blk;
+  uint64_t lo = 0, hi = n_long;  // is k a long block?
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (long_idx[mid] < row) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo < n_long && long_idx[lo] == row) return;
+  EvjSha o = evj_sha_begin(rows + threadIdx.x * BLK_ROW);
+  blk_emit(b, k, o, bs);
+  uint32_t be[8];
+  evj_sha_finish(o, be);
+  uint4 *dst = (uint4 *)(dig + 8 * row);
+  dst[0] = make_uint4(be[0], be[1], be[2], be[3]);
+  dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
+}
+
+// A shard's items name blocks of the whole batch; its digest and count arrays
+// are its own.  One lane per item: out[i] = item_block[i] - block_base, the
+// index the verify kernels and k_blk_tally use.
+__global__ void __launch_bounds__(256) k_blk_item_rebase(uint64_t n, const uint32_t *__restrict__ item_block,
+                                                         uint32_t block_base, uint32_t *__restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = item_block[i] - block_base;
 }
 
 // CheckBlock's tally: count[b] += the ACCEPT items of block b, one lane per
@@ -82,6 +123,28 @@ hipError_t blk_body_hash(hipStream_t st, const bv_block_batch &b, uint64_t b0, u
     hipLaunchKernelGGL(k_blk_body_hash<256>, grid1(b1 - b0, 256), dim3(256), 0, st, b, b0, b1, long_idx, n_long, dig);
   else
     return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t blk_body_hash_rb(hipStream_t st, const bv_block_batch &b, uint64_t b0, uint64_t b1,
+                            const uint64_t *long_idx, uint64_t n_long, const BlkBases &bs, uint32_t *dig, int nt) {
+  if (b1 <= b0) return hipSuccess;
+  if (nt == 0) nt = BLK_NT_DEFAULT;
+  if (nt == 64)
+    hipLaunchKernelGGL(k_blk_body_hash_rb<64>, grid1(b1 - b0, 64), dim3(64), 0, st, b, b0, b1, long_idx, n_long, bs,
+                       dig);
+  else if (nt == 256)
+    hipLaunchKernelGGL(k_blk_body_hash_rb<256>, grid1(b1 - b0, 256), dim3(256), 0, st, b, b0, b1, long_idx, n_long,
+                       bs, dig);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t blk_item_rebase(hipStream_t st, uint64_t n_items, const uint32_t *item_block, uint32_t block_base,
+                           uint32_t *out) {
+  if (n_items == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_blk_item_rebase, grid1(n_items, 256), dim3(256), 0, st, n_items, item_block, block_base, out);
   return hipGetLastError();
 }
 

@@ -30,8 +30,30 @@
 #define BLK_L7 ",\"InternalTransactions\":"
 #define BLK_L8 ",\"InternalTransactionReceipts\":"
 
+// Bases of a shard (bv_group_verify_blocks): the arrays of `k` are the slices
+// one block range [blk, ...) of a larger batch needs, and the values in them
+// (hash_off, tx_start, tx_off, itx_off, rcpt_off) are still the whole
+// batch's.  Wherever such a value indexes another array, its base — the value
+// at which that slice starts — is subtracted:
+//   blk   the per-block arrays start at block blk (hash_off and hash_nil at
+//         3 blk; b is the batch's index)
+//   hash  hash_off[3 blk]: hash_bytes starts at that byte
+//   tx    tx_start[blk]: tx_off and tx_nil start at that transaction
+//   txb   tx_off[tx_start[blk]]: tx_bytes starts at that byte
+//   itx   itx_off[blk], rcpt  rcpt_off[blk]: the fragment bytes start there
+// BlkNoBases (all zero, compile-time) is the whole batch: the subtractions
+// fold away and blk_len / blk_emit compile as they did without them.
+struct BlkBases {
+  uint64_t blk, hash, tx, txb, itx, rcpt;
+};
+struct BlkNoBases {
+  static constexpr uint64_t blk = 0, hash = 0, tx = 0, txb = 0, itx = 0, rcpt = 0;
+};
+
 // Body length of block b.
-DEV uint64_t blk_len(const bv_block_batch &k, uint64_t b) {
+template <class B = BlkNoBases>
+DEV uint64_t blk_len(const bv_block_batch &k, uint64_t b, const B &bs = B{}) {
+  b -= bs.blk;
   uint64_t n = EVJ_LEN(BLK_L0) + evj_dec_len(k.index[b]) + EVJ_LEN(BLK_L1) + evj_dec_len(k.round_received[b]) +
                EVJ_LEN(BLK_L2) + evj_dec_len(k.timestamp[b]) + EVJ_LEN(BLK_L3) + EVJ_LEN(BLK_L4) + EVJ_LEN(BLK_L5);
   for (int h = 0; h < 3; h++) {
@@ -42,7 +64,7 @@ DEV uint64_t blk_len(const bv_block_batch &k, uint64_t b) {
   if (k.tx_list_nil && k.tx_list_nil[b]) {
     n += 4;
   } else {
-    const uint64_t t0 = k.tx_start[b], t1 = k.tx_start[b + 1];
+    const uint64_t t0 = k.tx_start[b] - bs.tx, t1 = k.tx_start[b + 1] - bs.tx;
     n += 2 + (t1 > t0 ? t1 - t0 - 1 : 0);
     for (uint64_t t = t0; t < t1; t++)
       n += (k.tx_nil && k.tx_nil[t]) ? 4 : 2 + evj_b64_len(k.tx_off[t + 1] - k.tx_off[t]);
@@ -85,8 +107,9 @@ inline void blk_copy(EvjMem &o, const uint8_t *src, uint64_t n) {
 #endif
 
 // Block b's body into sink `o` (blk_len bytes).
-template <class O>
-DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o) {
+template <class O, class B = BlkNoBases>
+DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o, const B &bs = B{}) {
+  b -= bs.blk;
   evj_lit(o, BLK_L0);
   evj_dec(o, k.index[b]);
   evj_lit(o, BLK_L1);
@@ -100,7 +123,7 @@ DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o) {
       evj_lit(o, "null");
     } else {
       o.put('"');
-      blk_b64(o, k.hash_bytes + k.hash_off[i], k.hash_off[i + 1] - k.hash_off[i]);
+      blk_b64(o, k.hash_bytes + (k.hash_off[i] - bs.hash), k.hash_off[i + 1] - k.hash_off[i]);
       o.put('"');
     }
   }
@@ -108,7 +131,7 @@ DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o) {
   if (k.tx_list_nil && k.tx_list_nil[b]) {
     evj_lit(o, "null");
   } else {
-    const uint64_t t0 = k.tx_start[b], t1 = k.tx_start[b + 1];
+    const uint64_t t0 = k.tx_start[b] - bs.tx, t1 = k.tx_start[b + 1] - bs.tx;
     o.put('[');
     for (uint64_t t = t0; t < t1; t++) {
       if (t > t0) o.put(',');
@@ -116,7 +139,7 @@ DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o) {
         evj_lit(o, "null");
       } else {
         o.put('"');
-        blk_b64(o, k.tx_bytes + k.tx_off[t], k.tx_off[t + 1] - k.tx_off[t]);
+        blk_b64(o, k.tx_bytes + (k.tx_off[t] - bs.txb), k.tx_off[t + 1] - k.tx_off[t]);
         o.put('"');
       }
     }
@@ -125,14 +148,14 @@ DEV void blk_emit(const bv_block_batch &k, uint64_t b, O &o) {
   evj_lit(o, BLK_L7);
   const uint64_t il = evj_frag_len(k.itx_off, b);
   if (il) {
-    blk_copy(o, k.itx_json + k.itx_off[b], il);
+    blk_copy(o, k.itx_json + (k.itx_off[b] - bs.itx), il);
   } else {
     evj_lit(o, "null");
   }
   evj_lit(o, BLK_L8);
   const uint64_t rl = evj_frag_len(k.rcpt_off, b);
   if (rl) {
-    blk_copy(o, k.rcpt_json + k.rcpt_off[b], rl);
+    blk_copy(o, k.rcpt_json + (k.rcpt_off[b] - bs.rcpt), rl);
   } else {
     evj_lit(o, "null");
   }

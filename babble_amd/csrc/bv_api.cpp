@@ -618,7 +618,7 @@ extern "C" void bv_destroy(bv_ctx *ctx) {
   }
   if (ctx->g_table) gtable_release(ctx->device);
   DevBuf *bufs[] = {&ctx->d_in,     &ctx->kc_kxy, &ctx->kc_btabs,    &ctx->ev_iota,
-                    &ctx->d_stamps, &ctx->d_sig,  &ctx->d_blk_count};
+                    &ctx->d_stamps, &ctx->d_sig,  &ctx->d_blk_count, &ctx->d_blk_item};
   for (auto *b : bufs) b->release();
   for (auto &sl : ctx->slot) {
     DevBuf *sb[] = {&sl.digests,   &sl.kstatus, &sl.kxy, &sl.bases_jac, &sl.key_sub, &sl.key_pscr,
@@ -734,7 +734,8 @@ int bv_run_keys(bv_ctx *ctx, const bv_batch *b, hipEvent_t keys_ready, hipEvent_
   HIPCHK(hipStreamWaitEvent(ctx->sstream, s_ready, 0), BV_E_LAUNCH, "fork");
   if (d_sig) {  // signature text: r, s and pre (b's arrays, in ctx->d_sig) are decoded from it first
     const int rc = bv_sig_decode_launch(ctx, n_items, *d_sig, bv_sig_out{(uint8_t *)b->r_be, (uint8_t *)b->s_be,
-                                                                        (uint8_t *)b->pre});
+                                                                        (uint8_t *)b->pre},
+                                        d_sig->base);
     if (rc != BV_OK) return rc;
   }
   // items per lane: kPrepM amortises the inversion in large batches; a small

@@ -14,6 +14,11 @@
 // decision for every item, and k_blk_tally.  A batch the text entry would run
 // on its one-launch small path has its bodies built on the host and takes
 // that path (which hashes on the host already).
+//
+// The bulk pipeline is split as bv_verify_events' is: bv_validate_blocks over
+// the whole batch, bv_blocks_launch over one block range and its items, and
+// bv_blocks_finish.  bv_verify_blocks passes the whole range with zero bases;
+// bv_group_verify_blocks (bv_group.cpp) one shard per device slot.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -60,12 +65,12 @@ const char *check_fields(const bv_block_batch *k, CopyPool *pool) {
   return nullptr;
 }
 
-// body_off[b + 1] - body_off[b] = blk_len(b), body_off[0] = 0
-void body_lens(const bv_block_batch *k, CopyPool *pool, uint64_t *body_off) {
-  const uint64_t n = k->n_blocks;
+// blocks [b0, b1): body_off[b - b0 + 1] - body_off[b - b0] = blk_len(b), body_off[0] = 0
+void body_lens(const bv_block_batch *k, CopyPool *pool, uint64_t b0, uint64_t b1, uint64_t *body_off) {
+  const uint64_t n = b1 - b0;
   body_off[0] = 0;
-  par(pool, n, 1 << 12, [k, body_off](uint64_t lo, uint64_t hi) {
-    for (uint64_t b = lo; b < hi; b++) body_off[b + 1] = blk_len(*k, b);
+  par(pool, n, 1 << 12, [k, b0, body_off](uint64_t lo, uint64_t hi) {
+    for (uint64_t b = lo; b < hi; b++) body_off[b + 1] = blk_len(*k, b0 + b);
     return true;
   });
   for (uint64_t b = 0; b < n; b++) body_off[b + 1] += body_off[b];
@@ -78,7 +83,9 @@ void bodies(const bv_block_batch *k, CopyPool *pool, const uint64_t *body_off, u
   });
 }
 
-int validate(bv_ctx *ctx, const bv_block_batch *k, bool *text) {
+}  // namespace
+
+int bv_validate_blocks(bv_ctx *ctx, const bv_block_batch *k, bool *text) {
   if (const char *why = check_fields(k, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
   const uint64_t n = k->n_blocks, n_items = k->n_items;
   const uint32_t n_keys = k->n_keys;
@@ -106,46 +113,71 @@ int validate(bv_ctx *ctx, const bv_block_batch *k, bool *text) {
   return BV_OK;
 }
 
-int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uint32_t *valid_count) {
-  bv_host_call call;
-  call.t0 = std::chrono::steady_clock::now();
+namespace {
+
+// Whether the batch is small enough that the route needs its body lengths
+// before anything is staged.
+bool maybe_small_batch(bv_ctx *ctx, const bv_block_batch *k) {
+  return ctx->small_path && k->n_items &&
+         std::max(k->n_items, k->n_blocks) <= std::max(ctx->small_max, ctx->small_warm_max);
+}
+
+// The items as bv_batch items over the bodies as messages (ctx->blk_off: the
+// body offsets, filled by the caller); the route is decided from the offsets alone.
+bv_batch items_over_bodies(bv_ctx *ctx, const bv_block_batch *k, bool text) {
+  static const uint8_t kNoBytes[64] = {};
+  bv_batch hb = {};
+  hb.n_msgs = k->n_blocks;
+  hb.msg_bytes = kNoBytes;
+  hb.msg_off = ctx->blk_off.data();
+  hb.n_keys = k->n_keys;
+  hb.key_bytes = k->key_bytes;
+  hb.key_off = k->key_off;
+  hb.n_items = k->n_items;
+  hb.item_msg = k->item_block;
+  hb.item_key = k->item_key;
+  if (!text) hb.r_be = k->r_be, hb.s_be = k->s_be, hb.pre = k->pre;
+  return hb;
+}
+
+}  // namespace
+
+// The routing decision bv_verify_blocks makes for a validated batch: true when
+// it runs on the one-launch small path.  (bv_group_verify_blocks asks it for
+// the whole batch; the batch then goes to bv_verify_blocks on slot 0.)
+bool bv_blocks_small(bv_ctx *ctx, const bv_block_batch *k, bool text) {
+  if (!k->n_blocks || !maybe_small_batch(ctx, k)) return false;
+  ctx->blk_off.resize(k->n_blocks + 1);
+  body_lens(k, ctx->pool, 0, k->n_blocks, ctx->blk_off.data());
+  const bv_batch hb = items_over_bodies(ctx, k, text);
+  return bv_small_batch(ctx, &hb, text);
+}
+
+static int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uint32_t *valid_count) {
+  bv_blk_call call;
+  call.host.t0 = std::chrono::steady_clock::now();
   bool text = false;
-  int rc = validate(ctx, k, &text);
+  int rc = bv_validate_blocks(ctx, k, &text);
   if (rc != BV_OK) return rc;
   hipStream_t st = ctx->stream;
   ctx->timing = bv_timing{};
   ctx->last = st;
   const uint64_t n = k->n_blocks, n_items = k->n_items;
-  const uint32_t n_keys = k->n_keys;
   if (n == 0) return BV_OK;  // (validated: no items either)
 
   // Body lengths: the route (only a batch small enough to take the one-launch
   // path needs them before anything is staged) and the long bodies (bulk
-  // batches: found below, while the signatures cross PCIe).
+  // batches: found in bv_blocks_launch, while the signatures cross PCIe).
   std::vector<uint64_t> &body_off = ctx->blk_off;
   body_off.resize(n + 1);
-  const bool maybe_small =
-      ctx->small_path && n_items && std::max(n_items, n) <= std::max(ctx->small_max, ctx->small_warm_max);
-  if (maybe_small) body_lens(k, ctx->pool, body_off.data());
-
-  // the items as bv_batch items over the bodies as messages
-  static const uint8_t kNoBytes[64] = {};
-  bv_batch hb = {};
-  hb.n_msgs = n;
-  hb.msg_bytes = kNoBytes;  // (the route is decided from the offsets alone)
-  hb.msg_off = body_off.data();
-  hb.n_keys = n_keys;
-  hb.key_bytes = k->key_bytes;
-  hb.key_off = k->key_off;
-  hb.n_items = n_items;
-  hb.item_msg = k->item_block;
-  hb.item_key = k->item_key;
-  if (!text) hb.r_be = k->r_be, hb.s_be = k->s_be, hb.pre = k->pre;
-  const bv_sig_text htext{k->sig_off, k->sig_text};
+  const bool maybe_small = maybe_small_batch(ctx, k);
+  if (maybe_small) body_lens(k, ctx->pool, 0, n, body_off.data());
 
   // Small batches: the text entry's routing decision for the same item count
   // and keys; the bodies are built here and the one-launch path hashes them
   // on the host.  Its statuses land in host memory, where they are tallied.
+  bv_batch hb = items_over_bodies(ctx, k, text);
+  const bv_sig_text htext{k->sig_off, k->sig_text};
   if (maybe_small && bv_small_batch(ctx, &hb, text)) {
     ctx->blk_bodies.resize(body_off[n] + 64);
     bodies(k, ctx->pool, body_off.data(), ctx->blk_bodies.data());
@@ -169,12 +201,88 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
     return BV_OK;
   }
 
-  // ---- the bulk pipeline ----
+  // the bulk pipeline: the whole batch as one shard with zero bases
+  call.lens_done = maybe_small;
+  const bv_blk_shard whole{0, n, 0, n_items};
+  rc = bv_blocks_launch(ctx, k, whole, res, valid_count, &call, text);
+  if (rc != BV_OK) return rc;
+  rc = bv_mark_done(ctx, st);
+  if (rc != BV_OK) return rc;
+  return bv_blocks_finish(ctx, res, valid_count, &call, true);
+}
+
+int bv_blocks_finish(bv_ctx *ctx, bv_result *res, uint32_t *valid_count, bv_blk_call *call, bool bits_out) {
+  bv_batch sizes = {};
+  sizes.n_msgs = call->n_blocks;
+  sizes.n_items = call->n_items;
+  const int rc = bv_host_finish(ctx, &sizes, res, &call->host, bits_out);
+  if (rc != BV_OK) return rc;
+  if (valid_count && !call->direct_cnt) memcpy(valid_count, call->host.pout + call->o_cnt, call->n_blocks * 4);
+  return BV_OK;
+}
+
+// The bulk pipeline over blocks [sh.b0, sh.b1) of a validated batch and the
+// items [sh.i0, sh.i1) that name them: everything up to the call's last
+// enqueued command (the caller records the end with bv_mark_done and collects
+// with bv_blocks_finish).  bv_verify_blocks passes the whole batch;
+// bv_group_verify_blocks one shard per device slot.  The shard's slices are
+// staged from where they lie in the caller's arrays, and the values in them
+// stay the whole batch's: the serialiser subtracts the bases (blkjson.h
+// BlkBases), k_sig_decode the text's, and k_blk_item_rebase writes the items'
+// block indices less sh.b0 for the verify kernels and the tally, whose digest
+// and count arrays are the shard's.  With every base zero the un-based kernel
+// runs and the items are read as staged.  The long bodies are built on the
+// host from the whole batch.
+int bv_blocks_launch(bv_ctx *ctx, const bv_block_batch *whole, const bv_blk_shard &sh, const bv_result *res,
+                     uint32_t *valid_count, bv_blk_call *call_p, bool text_batch) {
+  bv_host_call &call = call_p->host;
+  int rc = BV_OK;
+  hipStream_t st = ctx->stream;
+  ctx->timing = bv_timing{};
+  ctx->last = st;
+  const uint64_t n = sh.b1 - sh.b0, n_items = sh.i1 - sh.i0;  // the shard's: b and i below are shard-local
+  call_p->n_blocks = n;
+  call_p->n_items = n_items;
+  if (n == 0) return BV_OK;
+  const uint32_t n_keys = whole->n_keys;
+  BlkBases bs = {};
+  bs.blk = sh.b0;
+  bs.hash = whole->hash_off[3 * sh.b0];
+  bs.tx = whole->tx_start[sh.b0];
+  bs.txb = whole->tx_start[whole->n_blocks] ? whole->tx_off[bs.tx] : 0;
+  bs.itx = whole->itx_off ? whole->itx_off[sh.b0] : 0;
+  bs.rcpt = whole->rcpt_off ? whole->rcpt_off[sh.b0] : 0;
+  const bool text = text_batch && n_items;  // (a shard of item-less blocks has no text to decode)
+  const uint64_t sig_base = text ? whole->sig_off[sh.i0] : 0;
+  const bool rebased = bs.blk || bs.hash || bs.tx || bs.txb || bs.itx || bs.rcpt;
+  // the shard's view of the caller's arrays (host pointers to its first elements)
+  bv_block_batch view = *whole;
+  {
+    auto adv = [](auto *&p, uint64_t by) {
+      if (p) p += by;
+    };
+    view.n_blocks = n;
+    view.n_items = n_items;
+    adv(view.index, sh.b0), adv(view.round_received, sh.b0), adv(view.timestamp, sh.b0);
+    adv(view.hash_off, 3 * sh.b0), adv(view.hash_bytes, bs.hash), adv(view.hash_nil, 3 * sh.b0);
+    adv(view.tx_start, sh.b0), adv(view.tx_off, bs.tx), adv(view.tx_bytes, bs.txb);
+    adv(view.tx_list_nil, sh.b0), adv(view.tx_nil, bs.tx);
+    adv(view.itx_off, sh.b0), adv(view.itx_json, bs.itx), adv(view.rcpt_off, sh.b0), adv(view.rcpt_json, bs.rcpt);
+    adv(view.item_block, sh.i0), adv(view.item_key, sh.i0);
+    adv(view.sig_off, sh.i0), adv(view.sig_text, sig_base);
+    adv(view.r_be, 32 * sh.i0), adv(view.s_be, 32 * sh.i0), adv(view.pre, sh.i0);
+  }
+  const bv_block_batch *k = &view;
+  std::vector<uint64_t> &body_off = ctx->blk_off;  // the shard's bodies (whole batch: maybe filled for the route)
+  const bool lens_done = call_p->lens_done;
+  if (!lens_done) body_off.resize(n + 1);
+
   const uint64_t key_len = n_keys ? k->key_off[n_keys] : 0;
-  const uint64_t n_tx = k->tx_start[n], tx_len = n_tx ? k->tx_off[n_tx] : 0;
-  const uint64_t hash_len = k->hash_off[3 * n];
-  const uint64_t itx_len = k->itx_off ? k->itx_off[n] : 0, rcpt_len = k->rcpt_off ? k->rcpt_off[n] : 0;
-  const uint64_t text_len = text ? k->sig_off[n_items] : 0;
+  const uint64_t n_tx = k->tx_start[n] - bs.tx, tx_len = n_tx ? k->tx_off[n_tx] - bs.txb : 0;
+  const uint64_t hash_len = k->hash_off[3 * n] - bs.hash;
+  const uint64_t itx_len = k->itx_off ? k->itx_off[n] - bs.itx : 0,
+                 rcpt_len = k->rcpt_off ? k->rcpt_off[n] - bs.rcpt : 0;
+  const uint64_t text_len = text ? k->sig_off[n_items] - sig_base : 0;
   StagePlan plan;
   auto add = [&](const void *src, size_t bytes, size_t pad = 0) { return plan.add(src, bytes, {}, 1, pad); };
   // the keys; the signature text or s / pre; the item arrays; the block fields
@@ -237,6 +345,10 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   d.key_off = (const uint64_t *)(dev + o_koff);
   d.n_items = n_items;
   d.item_msg = (const uint32_t *)(dev + o_ib);
+  if (bs.blk && n_items) {  // the shard's digest and count arrays are its own: k_blk_item_rebase, below
+    HIPCHK(ctx->d_blk_item.ensure(n_items * 4), BV_E_OOM, "alloc rebased item blocks");
+    d.item_msg = ctx->d_blk_item.as<uint32_t>();
+  }
   d.item_key = (const uint32_t *)(dev + o_ik);
   d.r_be = dev + o_r;
   d.s_be = dev + o_s;
@@ -245,6 +357,7 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   if (text) {  // decoded on the s^-1 stream (bv_run_keys) into ctx->d_sig
     dsig.off = (const uint64_t *)(dev + o_s);
     dsig.text = dev + o_pre;
+    dsig.base = sig_base;
     bv_sig_out so;
     rc = bv_sig_bufs(ctx, n_items, &so);
     if (rc != BV_OK) return rc;
@@ -272,7 +385,8 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
 
   // the block fields (the long blocks' too: they are a few); the list of the
   // long blocks goes with them, their digests follow
-  if (!maybe_small) body_lens(k, ctx->pool, body_off.data());  // (under the transfers enqueued so far)
+  // (under the transfers enqueued so far)
+  if (!lens_done) body_lens(whole, ctx->pool, sh.b0, sh.b1, body_off.data());
   std::vector<uint64_t> longb;
   for (uint64_t b = 0; b < n; b++)
     if (body_off[b + 1] - body_off[b] > kHostHashLen) longb.push_back(b);
@@ -321,14 +435,23 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   call.direct_hash = bv_is_pinned(res->msg_hash, n * 32);
   call.direct_status = n_items && bv_is_pinned(res->status, n_items);
   const bool direct_cnt = valid_count && bv_is_pinned(valid_count, n * 4);
+  call_p->o_cnt = o_cnt;
+  call_p->direct_cnt = direct_cnt;
   uint8_t *hout = call.direct_hash ? res->msg_hash : pout;
 
   if (ctx->has_done) HIPCHK(hipStreamWaitEvent(st, ctx->ev_done, 0), BV_E_LAUNCH, "order");
   HIPCHK(hipEventRecord(ev[E_HASH0], st), BV_E_LAUNCH, "event");
   HIPCHK(hipStreamWaitEvent(st, ev[E_SMALL], 0), BV_E_LAUNCH, "join block fields");
+  // (the item arrays landed before the fields; nothing before k_verify_gf reads item_msg: the key part does not)
+  if (d.item_msg != (const uint32_t *)(dev + o_ib))
+    HIPCHK(bvk::blk_item_rebase(st, n_items, (const uint32_t *)(dev + o_ib), (uint32_t)bs.blk,
+                                ctx->d_blk_item.as<uint32_t>()),
+           BV_E_LAUNCH, "k_blk_item_rebase");
   HIPCHK(hipEventRecord(ev[E_FORK], st), BV_E_LAUNCH, "event");  // ms_sha256: the build-and-hash kernel
-  HIPCHK(bvk::blk_body_hash(st, dk, 0, n, ctx->d_long.as<uint64_t>(), nl, pipe.o.dig, ctx->blk_nt), BV_E_LAUNCH,
-         "k_blk_body_hash");
+  HIPCHK(rebased ? bvk::blk_body_hash_rb(st, dk, sh.b0, sh.b1, ctx->d_long.as<uint64_t>(), nl, bs, pipe.o.dig,
+                                         ctx->blk_nt)
+                 : bvk::blk_body_hash(st, dk, 0, n, ctx->d_long.as<uint64_t>(), nl, pipe.o.dig, ctx->blk_nt),
+         BV_E_LAUNCH, "k_blk_body_hash");
   HIPCHK(hipEventRecord(ev[E_HASHED], st), BV_E_LAUNCH, "event");
   if (nl) {
     // the long bodies on the host (pool threads: blk_emit into scratch, SHA
@@ -339,7 +462,7 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
       for (uint64_t i = lo; i < hi; i++) {
         const uint64_t b = longb[i], len = body_off[b + 1] - body_off[b];
         body.resize(len);
-        blk_write(*k, b, body.data());
+        blk_write(*whole, sh.b0 + b, body.data());  // (the host reads the caller's whole arrays: no bases)
         hsha::digest(body.data(), len, ldig + 32 * i);
       }
       return true;
@@ -383,18 +506,8 @@ int verify_blocks_impl(bv_ctx *ctx, const bv_block_batch *k, bv_result *res, uin
   HIPCHK(hipStreamWaitEvent(st, ev[E_STAGED], 0), BV_E_LAUNCH, "join");  // staging free after this point
   HIPCHK(hipEventRecord(ev[E_CSDONE], cs), BV_E_LAUNCH, "event");  // the digests' d2h precedes ev_done
   HIPCHK(hipStreamWaitEvent(st, ev[E_CSDONE], 0), BV_E_LAUNCH, "join");
-  rc = bv_mark_done(ctx, st);
-  if (rc != BV_OK) return rc;
-  bv_batch sizes = {};
-  sizes.n_msgs = n;
-  sizes.n_items = n_items;
-  rc = bv_host_finish(ctx, &sizes, res, &call, true);
-  if (rc != BV_OK) return rc;
-  if (valid_count && !direct_cnt) memcpy(valid_count, pout + o_cnt, n * 4);
   return BV_OK;
 }
-
-}  // namespace
 
 extern "C" int bv_verify_blocks(bv_ctx *ctx, const bv_block_batch *blocks, bv_result *res, uint32_t *valid_count) {
   if (!ctx || !blocks || !res) return BV_E_ARGS;
@@ -407,7 +520,7 @@ extern "C" int bv_verify_blocks(bv_ctx *ctx, const bv_block_batch *blocks, bv_re
 extern "C" int bv_block_body_lens(const bv_block_batch *blocks, uint64_t *body_off) {
   if (!blocks || !body_off) return BV_E_ARGS;
   if (check_fields(blocks, nullptr)) return BV_E_ARGS;
-  body_lens(blocks, nullptr, body_off);
+  body_lens(blocks, nullptr, 0, blocks->n_blocks, body_off);
   return BV_OK;
 }
 

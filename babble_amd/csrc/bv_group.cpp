@@ -23,9 +23,10 @@
 // multi-device code path, so it runs on hardware with one GPU
 // (tests/test_gpu_cache_group.py::test_group_logical_shards).
 //
-// Two entries share the gather tail (gather_and_finish): bv_group_verify_batch
-// (serialized bodies, above) and bv_group_verify_events (wire fields, sharded
-// by event index; below).
+// Three entries share the gather tail (gather_and_finish):
+// bv_group_verify_batch (serialized bodies, above), bv_group_verify_events
+// (wire fields, sharded by event index) and bv_group_verify_blocks (block
+// fields, sharded by block; both below).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -476,6 +477,98 @@ extern "C" int bv_group_verify_events(bv_group *g, const bv_event_batch *eb, bv_
   if (!g || !eb || !res) return BV_E_ARGS;
   std::lock_guard<std::mutex> lk(g->mu);
   const int rc = group_verify_events(g, eb, res);
+  if (rc != BV_OK) drain_all(g, rc);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// bv_group_verify_blocks: the block entry (bv_verify_blocks) sharded by block
+// (each block's signatures stay on one device, so CheckBlock's
+// count is local).  The plan is bv_plan_block_shards'; every slot stages its
+// shard's slices of the caller's arrays as they are and the device subtracts
+// the shard's bases (bv_blocks_launch, blkjson.h BlkBases, k_blk_item_rebase).
+// Digests, statuses and counts come back per slot; only the accept bits go
+// through the gather.  A batch whose items are not sorted by block, or that
+// bv_verify_blocks runs on its one-launch small path, is one bv_verify_blocks
+// call on slot 0.
+// ---------------------------------------------------------------------------
+static int group_verify_blocks(bv_group *g, const bv_block_batch *k, bv_result *res, uint32_t *valid_count) {
+  const int D = (int)g->ctx.size();
+  bv_ctx *c0 = g->ctx[0];
+  bool text = false, whole = false;
+  {
+    std::lock_guard<std::mutex> clk(c0->mu);
+    const int rc = bv_validate_blocks(c0, k, &text);
+    if (rc != BV_OK) return gfail(g, rc, c0->err);
+    if (k->n_blocks == 0) return BV_OK;  // (validated: no items either)
+    // (the O(n) order check on the copy pool, as bv_group_verify_batch)
+    whole = !c0->pool->parallel_for(k->n_items > 0 ? k->n_items - 1 : 0, 1 << 17, [k](uint64_t lo, uint64_t hi) {
+      for (uint64_t i = lo; i < hi; i++)
+        if (k->item_block[i] > k->item_block[i + 1]) return false;
+      return true;
+    });
+    if (!whole) {
+      if (hipSetDevice(c0->device) != hipSuccess) return gfail(g, BV_E_NODEVICE, "hipSetDevice");
+      whole = bv_blocks_small(c0, k, text);
+    }
+  }
+  if (whole) {
+    const int rc = bv_verify_blocks(c0, k, res, valid_count);
+    return rc == BV_OK ? rc : gfail(g, rc, c0->err);
+  }
+  std::vector<uint64_t> bb(D + 1), ib(D + 1);
+  plan_block_bounds(k, D, bb.data(), ib.data());
+  uint64_t words = 1;
+  for (int d = 0; d < D; d++) words = std::max<uint64_t>(words, (ib[d + 1] - ib[d] + 63) / 64);
+
+  // stage, build, hash, verify and tally every shard concurrently (one host
+  // thread per slot); digests, statuses and counts go straight to the shard's
+  // part of the caller's buffers
+  auto shard_res = [&](int d) {
+    bv_result sr = {};
+    sr.msg_hash = res->msg_hash ? res->msg_hash + 32 * bb[d] : nullptr;
+    sr.status = res->status ? res->status + ib[d] : nullptr;
+    return sr;  // (no accept_bits: the shard's bits leave through the gather)
+  };
+  auto shard_cnt = [&](int d) { return valid_count ? valid_count + bb[d] : nullptr; };
+  std::vector<bv_blk_call> calls(D);
+  std::vector<int> rcs(D, BV_OK);
+  std::vector<std::thread> th;
+  for (int d = 0; d < D; d++)
+    th.emplace_back([&, d]() {
+      bv_ctx *c = g->ctx[d];
+      std::lock_guard<std::mutex> clk(c->mu);
+      if (hipSetDevice(c->device) != hipSuccess) {
+        rcs[d] = BV_E_NODEVICE;
+        return;
+      }
+      calls[d].host.t0 = std::chrono::steady_clock::now();
+      const bv_blk_shard sh{bb[d], bb[d + 1], ib[d], ib[d + 1]};
+      const bv_result sr = shard_res(d);
+      rcs[d] = bv_blocks_launch(c, k, sh, &sr, shard_cnt(d), &calls[d], text);
+      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.b1 > sh.b0 ? sh.i1 - sh.i0 : 0);
+    });
+  for (auto &t : th) t.join();
+  for (int d = 0; d < D; d++)
+    if (rcs[d] != BV_OK) return gfail(g, rcs[d], "device " + std::to_string(g->devices[d]) + ": " + g->ctx[d]->err);
+
+  std::vector<uint64_t> gathered;
+  const int rc = gather_and_finish(g, words, gathered, [&](int d, bv_ctx *c) {
+    if (bb[d + 1] == bb[d]) return (int)BV_OK;  // an empty shard launched nothing
+    bv_result sr = shard_res(d);
+    return bv_blocks_finish(c, &sr, shard_cnt(d), &calls[d], false);
+  });
+  if (rc != BV_OK) return rc;
+  if (res->accept_bits && bv_merge_shard_bits(gathered.data(), words, D, ib.data(), res->accept_bits) != BV_OK)
+    return gfail(g, BV_E_ARGS, "merge shard bits");
+  return BV_OK;
+}
+
+extern "C" int bv_group_verify_blocks(bv_group *g, const bv_block_batch *blocks, bv_result *res,
+                                      uint32_t *valid_count) {
+  if (!g || !blocks || !res) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const int rc = group_verify_blocks(g, blocks, res, valid_count);
   if (rc != BV_OK) drain_all(g, rc);
   return rc;
 }

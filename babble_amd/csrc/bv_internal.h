@@ -31,6 +31,7 @@
 #define KS_OK 0  // k_key_decode statuses (verify_core.h)
 
 struct EvjBases;
+struct BlkBases;
 namespace bvk {
 hipError_t sha256(hipStream_t, uint64_t, const uint8_t *, const uint64_t *, uint32_t *, uint64_t max_len = ~0ull);
 hipError_t put_digests(hipStream_t, uint64_t, const uint64_t *, const uint32_t *, uint32_t *);
@@ -44,6 +45,13 @@ hipError_t ev_body_hash_rb(hipStream_t st, const bv_event_batch &b, uint64_t e0,
 // (sorted, n_long of them; device array) are skipped.  nt: lanes per workgroup, 64 or 256 (0: the default)
 hipError_t blk_body_hash(hipStream_t st, const bv_block_batch &b, uint64_t b0, uint64_t b1, const uint64_t *long_idx,
                          uint64_t n_long, uint32_t *dig, int nt = 0);
+// the same over a shard's slices (blkjson.h BlkBases): [b0, b1) are the whole batch's block indices; dig and
+// long_idx are the shard's (block k is row k - bs.blk of both)
+hipError_t blk_body_hash_rb(hipStream_t st, const bv_block_batch &b, uint64_t b0, uint64_t b1,
+                            const uint64_t *long_idx, uint64_t n_long, const BlkBases &bs, uint32_t *dig, int nt = 0);
+// out[i] = item_block[i] - block_base: a shard's items over its own digest and count arrays
+hipError_t blk_item_rebase(hipStream_t st, uint64_t n_items, const uint32_t *item_block, uint32_t block_base,
+                           uint32_t *out);
 // count[item_block[i]] += 1 for every item whose status is BV_ACCEPT (count zeroed by the caller)
 hipError_t blk_tally(hipStream_t st, uint64_t n_items, const uint32_t *item_block, const uint8_t *status,
                      uint32_t *count);
@@ -241,6 +249,7 @@ struct bv_ctx {
   DevBuf ev_iota;
   // bv_verify_blocks: valid_count on the device; the bodies a small batch builds on the host and their offsets
   DevBuf d_blk_count;
+  DevBuf d_blk_item;  // a shard's item -> block indices less its first block (k_blk_item_rebase)
   std::vector<uint8_t> blk_bodies;
   std::vector<uint64_t> blk_off;
   int blk_nt = 0;  // BV_BLK_NT (A/B knob): lanes per workgroup of k_blk_body_hash, 64 or 256 (0: the default)
@@ -334,6 +343,7 @@ int bv_validate_host_batch(bv_ctx *ctx, const bv_batch *b, bool text = false);
 struct bv_sig_text {
   const uint64_t *off = nullptr;
   const uint8_t *text = nullptr;
+  uint64_t base = 0;  // device pointers of a shard: `off` holds the whole batch's offsets, `text` starts at this byte
 };
 // The decoded r, s and pre of n signatures in ctx->d_sig (device arrays).
 struct bv_sig_out {
@@ -441,4 +451,28 @@ int bv_validate_events(bv_ctx *ctx, const bv_event_batch *eb);
 int bv_events_launch(bv_ctx *ctx, const bv_event_batch *eb, const bv_ev_shard &sh, const bv_result *res,
                      bv_host_call *call);
 int bv_events_finish(bv_ctx *ctx, uint64_t n_events, bv_result *res, bv_host_call *call, bool bits_out);
+// bv_verify_blocks' bulk pipeline over one block range of a batch
+// (bv_blocks.cpp): blocks [b0, b1) and the items [i0, i1) that name them
+// (bv_plan_block_shards).  bv_validate_blocks checks the WHOLE batch once
+// (*text: the items' signatures come as text); bv_blocks_small is the routing
+// decision of bv_verify_blocks for the whole batch (the one-launch small
+// path); bv_blocks_launch enqueues the range's staging, hashing, verify and
+// tally (`res`, `valid_count`: the range's result pointers, reached by DMA
+// when pinned) and bv_blocks_finish collects after bv_mark_done.  An empty
+// block range launches nothing (skip its finish).
+struct bv_blk_shard {
+  uint64_t b0, b1, i0, i1;
+};
+struct bv_blk_call {
+  bv_host_call host;
+  uint64_t n_blocks = 0, n_items = 0;  // the range's
+  size_t o_cnt = 0;                    // its counts in host.pout, unless direct_cnt
+  bool direct_cnt = false;
+  bool lens_done = false;  // ctx->blk_off already holds the range's body offsets (the route needed them)
+};
+int bv_validate_blocks(bv_ctx *ctx, const bv_block_batch *blocks, bool *text);
+bool bv_blocks_small(bv_ctx *ctx, const bv_block_batch *blocks, bool text);
+int bv_blocks_launch(bv_ctx *ctx, const bv_block_batch *blocks, const bv_blk_shard &sh, const bv_result *res,
+                     uint32_t *valid_count, bv_blk_call *call, bool text);
+int bv_blocks_finish(bv_ctx *ctx, bv_result *res, uint32_t *valid_count, bv_blk_call *call, bool bits_out);
 void bv_read_timing(bv_ctx *ctx);

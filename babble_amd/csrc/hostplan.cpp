@@ -8,7 +8,9 @@
 //                        item shards, message partition;
 //   bv_merge_shard_bits  the accept bitmask from the all-gathered shard words;
 //   bv_plan_event_shards the plan of bv_group_verify_events: 64-aligned event
-//                        shards and each shard's range of parent hashes.
+//                        shards and each shard's range of parent hashes;
+//   bv_plan_block_shards the plan of bv_group_verify_blocks: bv_plan_group's
+//                        item shards and message partition over the blocks.
 //
 // Pure C++ so the same source links into the ASan/UBSan fuzz harnesses
 // (tests/hostfuzz, tests/hostfuzz_events) and into libbabbleverify.so.
@@ -157,6 +159,44 @@ void plan_group(const bv_batch *b, int D, GroupPlan &p, bv_batch &sorted, int in
     prev = p.mlo[d];
   }
   for (int d = 0; d < D; d++) p.mhi[d] = d + 1 < D ? p.mlo[d + 1] : b->n_msgs;
+}
+
+// The plan of bv_group_verify_blocks for item_block non-decreasing: plan_group
+// over the items as bv_batch items with item_msg = item_block and n_msgs =
+// n_blocks (no second rule).
+void plan_block_bounds(const bv_block_batch *k, int D, uint64_t *block_bounds, uint64_t *item_bounds) {
+  bv_batch v = {};
+  v.n_msgs = k->n_blocks;
+  v.n_items = k->n_items;
+  v.item_msg = k->item_block;
+  GroupPlan p;
+  bv_batch sorted;
+  plan_group(&v, D, p, sorted, 1);
+  for (int d = 0; d <= D; d++) item_bounds[d] = p.bounds[d];
+  for (int d = 0; d < D; d++) block_bounds[d] = p.mlo[d];
+  block_bounds[D] = k->n_blocks;
+}
+
+void plan_blocks_whole(const bv_block_batch *k, int D, uint64_t *block_bounds, uint64_t *item_bounds) {
+  block_bounds[0] = item_bounds[0] = 0;
+  for (int d = 1; d <= D; d++) block_bounds[d] = k->n_blocks, item_bounds[d] = k->n_items;
+}
+
+extern "C" int bv_plan_block_shards(const bv_block_batch *k, int n_shards, uint64_t *block_bounds,
+                                    uint64_t *item_bounds) {
+  if (!k || n_shards <= 0 || !block_bounds || !item_bounds) return BV_E_ARGS;
+  if (k->n_items && !k->item_block) return BV_E_ARGS;
+  bool in_order = true;
+  for (uint64_t i = 0; i < k->n_items; i++) {
+    if (k->item_block[i] >= k->n_blocks) return BV_E_ARGS;
+    if (i && k->item_block[i] < k->item_block[i - 1]) in_order = false;
+  }
+  if (!in_order) {
+    plan_blocks_whole(k, n_shards, block_bounds, item_bounds);
+    return 1;
+  }
+  plan_block_bounds(k, n_shards, block_bounds, item_bounds);
+  return 0;
 }
 
 extern "C" int bv_plan_group(const bv_batch *b, int n_shards, uint64_t *item_bounds, uint64_t *msg_bounds,

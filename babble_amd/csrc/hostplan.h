@@ -22,6 +22,12 @@ struct GroupPlan {
 // knows (-1: checked here).
 void plan_group(const bv_batch *b, int D, GroupPlan &p, bv_batch &sorted, int in_order = -1);
 
+// The two outcomes of bv_plan_block_shards, D + 1 block and item bounds each:
+// plan_group over the blocks' items (item_block non-decreasing and < n_blocks,
+// checked by the caller), or the whole batch on shard 0: {0, n, n, ...}.
+void plan_block_bounds(const bv_block_batch *k, int D, uint64_t *block_bounds, uint64_t *item_bounds);
+void plan_blocks_whole(const bv_block_batch *k, int D, uint64_t *block_bounds, uint64_t *item_bounds);
+
 // The two halves of bv_plan_event_shards, for bv_group_verify_events (each
 // shard's host thread finds its own hash range, in pieces on its copy pool).
 // D + 1 event bounds: whole 64-event words per shard, or {0, n, n, ...} (dag).

@@ -466,7 +466,7 @@ def check_block(block: Block, peer_set: PeerSet, verifier=None) -> Optional[str]
     return None
 
 
-def check_blocks(blocks: Sequence[Block], peer_sets: Sequence[PeerSet], verifier=None) -> List[object]:
+def check_blocks(blocks: Sequence[Block], peer_sets: Sequence[PeerSet], verifier=None, group=None) -> List[object]:
     """Hashgraph.CheckBlock for every (block, peer set) pair in ONE
     bv_verify_blocks call: per block exactly what check_block returns (None
     or the error text).  Where check_block raises ReferencePanic, that
@@ -474,7 +474,9 @@ def check_blocks(blocks: Sequence[Block], peer_sets: Sequence[PeerSet], verifier
     way).  The bodies go to the library as fields; the count of valid
     signatures per block is the library's valid_count (tallied on the
     device for bulk batches); only signatures of validators in the block's
-    peer set are listed, as CheckBlock skips the others before Block.Verify."""
+    peer set are listed, as CheckBlock skips the others before Block.Verify.
+    group: a verifier.Group; the one verify_blocks call then goes to it
+    (bv_group_verify_blocks: sharded by block); PeerSet.Hash stays on `verifier`."""
     out: List[object] = [None] * len(blocks)
     kb = BlockBatchBuilder()
     slot = []  # (position in `blocks`, block index in the batch, its items)
@@ -489,7 +491,7 @@ def check_blocks(blocks: Sequence[Block], peer_sets: Sequence[PeerSet], verifier
         slot.append((i, m, items))
     if not slot:
         return out
-    res = (verifier or default_verifier()).verify_blocks(kb.pack(), counts=True)
+    res = (group or verifier or default_verifier()).verify_blocks(kb.pack(), counts=True)
     for i, m, items in slot:
         if any(int(res.status[k]) == REF_PANIC for k in items):
             out[i] = ReferencePanic("Block.Verify panics")

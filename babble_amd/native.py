@@ -42,6 +42,7 @@ EXPORTS = (
     "bv_verify_blocks", "bv_block_body_lens", "bv_block_bodies",
     "bv_verify_events_itx", "bv_itx_body_lens", "bv_itx_bodies", "bv_event_itx_body_lens", "bv_event_itx_bodies",
     "bv_verify_events_fields", "bv_event_fields_body_lens", "bv_event_fields_bodies",
+    "bv_group_verify_blocks", "bv_plan_block_shards",
 )
 
 
@@ -214,6 +215,10 @@ def lib() -> ctypes.CDLL:
     L.bv_group_kc_register.restype = ctypes.c_int
     L.bv_plan_event_shards.argtypes = [P, ctypes.c_int, P, P, P]
     L.bv_plan_event_shards.restype = ctypes.c_int
+    L.bv_group_verify_blocks.argtypes = [P, ctypes.POINTER(BvBlockBatch), ctypes.POINTER(BvResult), P]
+    L.bv_group_verify_blocks.restype = ctypes.c_int
+    L.bv_plan_block_shards.argtypes = [ctypes.POINTER(BvBlockBatch), ctypes.c_int, P, P]
+    L.bv_plan_block_shards.restype = ctypes.c_int
     L.bv_arena_create.argtypes = [ctypes.POINTER(P)]
     L.bv_arena_create.restype = ctypes.c_int
     L.bv_arena_destroy.argtypes = [P]

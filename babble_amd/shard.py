@@ -92,6 +92,19 @@ def plan_event_shards(parent_kind, parent_ref, n_shards: int):
     return dag, bounds, lo, hi
 
 
+def plan_block_shards(item_block, n_blocks: int, n_shards: int):
+    """bv_plan_block_shards (csrc/hostplan.cpp) restated: (unsorted,
+    block_bounds, item_bounds).  Items sorted by block follow `plan_group`
+    with the blocks as messages: item shards balanced by count that never
+    split a block's items, and a partition of the blocks cut at each shard's
+    first block.  Unsorted items stay whole on shard 0: [0, n, n, ...]."""
+    ib = np.asarray(item_block, dtype=np.int64)
+    permuted, _, bounds, mb = plan_group(ib, n_blocks, n_shards)
+    if permuted:
+        return True, [0] + [n_blocks] * n_shards, [0] + [len(ib)] * n_shards
+    return False, [int(x) for x in mb], [int(x) for x in bounds]
+
+
 def merge_bits(shard_words: Sequence[np.ndarray], bounds: Sequence[int]) -> np.ndarray:
     """Global accept bitmask from per-shard bitmasks whose bit 0 is the
     shard's first item (the host merge after bv_group's all-gather)."""

@@ -514,6 +514,31 @@ class Group:
         self._check(self._L.bv_group_verify_events(self._g, ctypes.byref(cb), ctypes.byref(r)))
         return res
 
+    def verify_blocks(self, pb, counts: bool = True, status: bool = True) -> "BlockVerifyResult":
+        """bv_group_verify_blocks over a batch.PackedBlockBatch: a batch whose
+        items are sorted by block is sharded by block, each device slot
+        building, hashing, verifying and tallying its shard; any other batch
+        (and one small enough for the one-launch path) runs on slot 0.
+        counts / status: as Verifier.verify_blocks."""
+        nb, ni, nw = max(pb.n_blocks, 1), max(pb.n_items, 1), max((pb.n_items + 63) // 64, 1)
+        res = BlockVerifyResult(np.empty((nb, 32), np.uint8), np.empty(ni, np.uint8) if status else None,
+                                np.empty(nw, np.uint64), np.empty(nb, np.uint32) if counts else None)
+        self.verify_blocks_into(pb, res)
+        return BlockVerifyResult(res.msg_hash[: pb.n_blocks], res.status[: pb.n_items] if status else None,
+                                 res.accept_bits[: (pb.n_items + 63) // 64],
+                                 res.valid_count[: pb.n_blocks] if counts else None)
+
+    def verify_blocks_into(self, pb, res: "BlockVerifyResult") -> "BlockVerifyResult":
+        """bv_group_verify_blocks into caller-owned result arrays, any of them
+        None (PinnedArena arrays are reached by DMA from every device; so are
+        the fields of a batch built by PinnedArena.block_batch)."""
+        keep: list = []
+        cb = pb.c_struct(keep)
+        r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
+        vc = getattr(res, "valid_count", None)
+        self._check(self._L.bv_group_verify_blocks(self._g, ctypes.byref(cb), ctypes.byref(r), _p(vc) or None))
+        return res
+
     def register_keys(self, pubkeys: Sequence[bytes]) -> None:
         """bv_group_kc_register: the validator set for every slot's key cache
         (a group created with F_KEY_CACHE)."""
@@ -558,6 +583,19 @@ def plan_event_shards(eb, n_shards: int):
     if rc < 0:
         raise native.BvError(rc, "bv_plan_event_shards")
     return bool(rc), bounds, lo[:n_shards], hi[:n_shards]
+
+
+def plan_block_shards(pb, n_shards: int):
+    """bv_plan_block_shards: (unsorted, block_bounds, item_bounds) — the plan
+    bv_group_verify_blocks follows for a batch.PackedBlockBatch (host only)."""
+    keep: list = []
+    cb = pb.c_struct(keep)
+    bb = np.zeros(n_shards + 1, np.uint64)
+    ib = np.zeros(n_shards + 1, np.uint64)
+    rc = native.lib().bv_plan_block_shards(ctypes.byref(cb), n_shards, bb.ctypes.data, ib.ctypes.data)
+    if rc < 0:
+        raise native.BvError(rc, "bv_plan_block_shards")
+    return bool(rc), bb, ib
 
 
 def merge_shard_bits(gathered: np.ndarray, words_per_shard: int, bounds) -> np.ndarray:

@@ -619,6 +619,42 @@ int bv_verify_blocks(bv_ctx *ctx, const bv_block_batch *blocks, bv_result *resul
 int bv_block_body_lens(const bv_block_batch *blocks, uint64_t *body_off /* n_blocks + 1 */);
 int bv_block_bodies(const bv_block_batch *blocks, const uint64_t *body_off, uint8_t *out);
 
+/* bv_verify_blocks over the group: blocks from their fields, sharded by block
+ * (each block's signatures stay on one device, so its count is local).  The
+ * result contract, the validation rules with their BV_E_ARGS cases and texts
+ * (checked once over the whole batch) and the pinned-memory rule are
+ * bv_verify_blocks'; msg_hash, status, accept_bits and valid_count may each
+ * be NULL (status == NULL with valid_count included).
+ * A batch whose item_block is non-decreasing is cut by bv_plan_block_shards:
+ * item shards balanced by count that never split a block's items, and a
+ * partition of the blocks, so blocks without items are hashed too.  Each
+ * non-empty shard takes the bulk pipeline on its slot, however small it is
+ * (an empty shard launches nothing), and writes its digests, statuses and
+ * counts straight into the caller's buffers at its block / item bounds; only
+ * the accept bitmasks go through the gather of bv_group_verify_batch, merged
+ * at the item bounds (not multiples of 64).  A shard ships the keys (whole),
+ * its block range of every per-block array, the matching ranges of the hash,
+ * transaction and fragment bytes, and its item range of item_block, item_key
+ * and the signature text or r_be / s_be / pre.  The slices keep the caller's
+ * values (nothing is rewritten on the host): the device subtracts the shard's
+ * bases.
+ * A batch whose items are NOT sorted by block, or that bv_verify_blocks runs
+ * on its one-launch small path (its routing decision, for the whole batch),
+ * is not sharded: it runs as one bv_verify_blocks call on device slot 0.
+ * After a failed call nothing stays in flight on any slot. */
+int bv_group_verify_blocks(bv_group *g, const bv_block_batch *blocks, bv_result *result,
+                           uint32_t *valid_count /* n_blocks, may be NULL */);
+/* Host helper (no device): the plan bv_group_verify_blocks follows.  Only
+ * n_blocks, n_items and item_block are read.  Returns 0 when item_block is
+ * non-decreasing: the plan is bv_plan_group's for a bv_batch with item_msg =
+ * item_block and n_msgs = n_blocks (item_bounds: bv_plan_shards'; block_bounds:
+ * its msg_bounds, a partition of [0, n_blocks)).  Returns 1 when it is not
+ * sorted: block_bounds = {0, n_blocks, n_blocks, ...}, item_bounds = {0,
+ * n_items, n_items, ...} (the whole batch on slot 0).  BV_E_ARGS on NULL
+ * pointers, n_shards <= 0 or item_block >= n_blocks. */
+int bv_plan_block_shards(const bv_block_batch *blocks, int n_shards, uint64_t *block_bounds /* n_shards + 1 */,
+                         uint64_t *item_bounds /* n_shards + 1 */);
+
 /* SHA-256 of n messages (host buffers) -> 32*n bytes. */
 int bv_sha256_batch(bv_ctx *ctx, uint64_t n_msgs, const uint8_t *msg_bytes,
                     const uint64_t *msg_off, uint8_t *out_hash);
