@@ -8,7 +8,8 @@ device handle (verifier) and a mirror of the reference's Go interface
 """
 from .native import ACCEPT, REF_PANIC, REJECT, REJECT_ERR, BvError, ReferencePanic  # noqa: F401
 
-from .verifier import Group, Verifier, plan_block_shards, plan_event_shards  # noqa: F401
+from .verifier import (Group, Verifier, plan_block_shards, plan_event_fields_shards,  # noqa: F401
+                       plan_event_shards)
 
 __all__ = ["ACCEPT", "REJECT", "REJECT_ERR", "REF_PANIC", "BvError", "ReferencePanic", "Group", "Verifier",
-           "plan_block_shards", "plan_event_shards"]
+           "plan_block_shards", "plan_event_fields_shards", "plan_event_shards"]

@@ -20,6 +20,22 @@
 #define BSIG_L1 ",\"Index\":"
 #define BSIG_L2 ",\"Signature\":"
 
+// Bases of a shard (bv_group_verify_events_fields), as EvjBases / ItxBases: the
+// block-signature arrays of `f` are the slices one event range of a larger
+// batch needs, and the values in bsig_start, bsig_sig_off and bsig_val_off are
+// still the whole batch's.
+//   bsig  bsig_start[a]: the per-signature arrays start at that signature
+//   sig   bsig_sig_off[bsig]: bsig_sig starts at that byte
+//   val   bsig_val_off[bsig] (0 when no entry is BV_BSIG_VAL_BYTES: the array
+//         is not read then): bsig_val_bytes starts at that byte
+// BsigNoBases (all zero, compile-time) is the whole batch.
+struct BsigBases {
+  uint64_t bsig, sig, val;
+};
+struct BsigNoBases {
+  static constexpr uint64_t bsig = 0, sig = 0, val = 0;
+};
+
 DEV uint8_t bsig_val_kind(const bv_event_fields_batch &f, uint64_t j) {
   return f.bsig_val_kind ? f.bsig_val_kind[j] : (uint8_t)BV_BSIG_VAL_CREATOR;
 }
@@ -29,8 +45,8 @@ DEV uint8_t bsig_val_kind(const bv_event_fields_batch &f, uint64_t j) {
 // chosen per lane between two of the batch's arrays must not be formed, the
 // array bases are wave-uniform values.  tests/test_gpu_event_fields.py runs
 // CREATOR, BYTES and NIL entries side by side in one wave.)
-template <class O>
-DEV void bsig_elem_emit(const bv_event_fields_batch &f, uint64_t e, uint64_t j, O &o) {
+template <class O, class B = BsigNoBases>
+DEV void bsig_elem_emit(const bv_event_fields_batch &f, uint64_t e, uint64_t j, O &o, const B &bs = B{}) {
   const bv_event_batch &b = f.ev.events;
   const uint8_t kind = bsig_val_kind(f, j);
   evj_lit(o, BSIG_L0);
@@ -38,7 +54,7 @@ DEV void bsig_elem_emit(const bv_event_fields_batch &f, uint64_t e, uint64_t j, 
     evj_lit(o, "null");
   } else if (kind == BV_BSIG_VAL_BYTES) {
     o.put('"');
-    evj_b64(o, f.bsig_val_bytes + f.bsig_val_off[j], f.bsig_val_off[j + 1] - f.bsig_val_off[j]);
+    evj_b64(o, f.bsig_val_bytes + (f.bsig_val_off[j] - bs.val), f.bsig_val_off[j + 1] - f.bsig_val_off[j]);
     o.put('"');
   } else {
     const uint32_t c = b.creator[e];
@@ -49,7 +65,7 @@ DEV void bsig_elem_emit(const bv_event_fields_batch &f, uint64_t e, uint64_t j, 
   evj_lit(o, BSIG_L1);
   evj_dec(o, f.bsig_index[j]);
   evj_lit(o, BSIG_L2);
-  gojson_string(o, f.bsig_sig + f.bsig_sig_off[j], f.bsig_sig_off[j + 1] - f.bsig_sig_off[j]);
+  gojson_string(o, f.bsig_sig + (f.bsig_sig_off[j] - bs.sig), f.bsig_sig_off[j + 1] - f.bsig_sig_off[j]);
   o.put('}');
 }
 
@@ -79,17 +95,17 @@ DEV uint64_t bsig_list_len(const bv_event_fields_batch &f, uint64_t e) {
   return n;
 }
 
-template <class O>
-DEV void bsig_list_emit(const bv_event_fields_batch &f, uint64_t e, O &o) {
+template <class O, class B = BsigNoBases>
+DEV void bsig_list_emit(const bv_event_fields_batch &f, uint64_t e, O &o, const B &bs = B{}) {
   if (bsig_list_is_nil(f, e)) {
     evj_lit(o, "null");
     return;
   }
-  const uint64_t j0 = f.bsig_start[e], j1 = f.bsig_start[e + 1];
+  const uint64_t j0 = f.bsig_start[e] - bs.bsig, j1 = f.bsig_start[e + 1] - bs.bsig;
   o.put('[');
   for (uint64_t j = j0; j < j1; j++) {
     if (j > j0) o.put(',');
-    bsig_elem_emit(f, e, j, o);
+    bsig_elem_emit(f, e, j, o, bs);
   }
   o.put(']');
 }
@@ -111,18 +127,21 @@ DEV uint64_t evj_len(const bv_event_fields_batch &f, uint64_t e, uint32_t ppos[2
   return evj_len_tail(b, e, n + bsig_list_len(f, e));
 }
 
-template <class O>
-DEV void evj_emit(const bv_event_fields_batch &f, uint64_t e, O &o) {
+// (bs, ib, sb: a shard's bases; `e` is then the whole batch's index, as evj_emit's)
+template <class O, class B = EvjNoBases, class IB = ItxNoBases, class SB = BsigNoBases>
+DEV void evj_emit(const bv_event_fields_batch &f, uint64_t e, O &o, const B &bs = B{}, const IB &ib = IB{},
+                  const SB &sb = SB{}) {
   const bv_event_batch &b = f.ev.events;
-  evj_emit_txs(b, e, o);
+  e -= bs.ev;
+  evj_emit_txs(b, e, o, bs);
   if (f.ev.itx_start) {
-    itx_list_emit(f.ev, e, o);
+    itx_list_emit(f.ev, e, o, ib);
   } else {
     if (evf_itx_empty(f, e)) evj_lit(o, "[]");
     else evj_lit(o, "null");
   }
-  evj_emit_mid(b, e, o);
-  bsig_list_emit(f, e, o);
+  evj_emit_mid(b, e, o, bs);
+  bsig_list_emit(f, e, o, sb);
   evj_emit_tail(b, e, o);
 }
 

@@ -98,6 +98,71 @@ int64_t decode_key(const bv_event_itx_batch *x, uint64_t i, uint8_t *out, std::v
   return k;
 }
 
+// What the host builds for the events [a, z) of a validated batch and the ITXs
+// they own (the whole batch for the single-context entries, one shard for the
+// group's): every array here is indexed from the range's first event / ITX, so
+// none of them needs a base on the device.
+struct EvfPrep {
+  uint64_t i0 = 0, m = 0;  // the range's ITXs are the batch's [i0, i0 + m)
+  // the ITX keys decoded at a fixed stride, their lengths, the forced-panic flags
+  std::vector<uint8_t> kfix, klen, force;
+  std::vector<uint64_t> koff;        // the combined key offsets: the creators' keys whole, then the distinct ITX keys
+  std::vector<uint32_t> ikey, usrc;  // ITX i's key slot; the ITX whose bytes fill slot n_keys + u
+  std::vector<uint64_t> soff;        // the signature-text offsets: the range's events', then its ITXs' Signature strings
+};
+
+// The ITX keys: decoded at a fixed stride by the pool, then packed behind the
+// creators' keys, one slot per DISTINCT key: an ITX whose key equals a
+// creator's or an earlier ITX's names that slot (a SyncResponse's ITXs are
+// about a few peers: the batch keeps its per-key tables and key-cache hits).
+// Then the signature text's offsets.
+int evf_prep(bv_ctx *ctx, const bv_event_itx_batch *x, bool itx_fields, uint64_t a, uint64_t z, EvfPrep &p) {
+  const bv_event_batch *eb = &x->events;
+  const uint64_t n = z - a, i0 = itx_fields ? x->itx_start[a] : 0, m = itx_fields ? x->itx_start[z] - i0 : 0;
+  p.i0 = i0, p.m = m;
+  const uint32_t n_keys = eb->n_keys;
+  if ((uint64_t)n_keys + m > 0xFFFFFFFFull) return bv_fail(ctx, BV_E_ARGS, "more than 2^32 keys");
+  p.kfix.resize(m * kItxKeyMax), p.klen.resize(m), p.force.resize(m);
+  if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
+    std::vector<uint8_t> big;
+    for (uint64_t i = lo; i < hi; i++) {
+      const int64_t k = decode_key(x, i0 + i, p.kfix.data() + i * kItxKeyMax, big);
+      p.force[i] = k < 0;
+      p.klen[i] = k < 0 ? 0 : (uint8_t)k;
+    }
+    return true;
+  });
+  std::vector<uint64_t> &koff = p.koff;
+  koff.assign(eb->key_off, eb->key_off + n_keys + 1);
+  p.ikey.resize(m);
+  {
+    std::unordered_map<std::string, uint32_t> slot;
+    for (uint32_t k = 0; k < n_keys; k++)
+      slot.emplace(koff[k + 1] > koff[k] ? std::string((const char *)eb->key_bytes + koff[k], koff[k + 1] - koff[k])
+                                         : std::string(),
+                   k);
+    for (uint64_t i = 0; i < m; i++) {
+      const auto ins = slot.emplace(std::string((const char *)p.kfix.data() + i * kItxKeyMax, p.klen[i]),
+                                    (uint32_t)(n_keys + p.usrc.size()));
+      if (ins.second) {
+        p.usrc.push_back((uint32_t)i);
+        koff.push_back(koff.back() + p.klen[i]);
+      }
+      p.ikey[i] = ins.first->second;
+    }
+  }
+  // the signature text: the events', then the ITXs' Signature strings
+  const uint64_t sig_base = eb->sig_off[a];
+  p.soff.resize(n + m + 1);
+  if (sig_base == 0) {
+    memcpy(p.soff.data(), eb->sig_off + a, (n + 1) * 8);
+  } else {
+    for (uint64_t e = 0; e <= n; e++) p.soff[e] = eb->sig_off[a + e] - sig_base;
+  }
+  for (uint64_t i = 0; i < m; i++) p.soff[n + i + 1] = p.soff[n + i] + itx_str_len(*x, i0 + i, ITX_SIGNATURE);
+  return BV_OK;
+}
+
 // Event.Verify's fold on the host (the small path; k_ev_compose otherwise)
 void compose_host(const bv_event_itx_batch *x, const uint8_t *item_status, const uint8_t *force, bv_result *res,
                   bv_event_itx_out *out) {
@@ -128,11 +193,11 @@ void compose_host(const bv_event_itx_batch *x, const uint8_t *item_status, const
 // them on the host (hostsha) and verifies the items in one launch, and the
 // fold is done on the host.  *taken = false: the bulk pipeline's.
 int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
-                bv_event_itx_out *out, bool dag,
-                const std::vector<uint32_t> &order, const std::vector<uint32_t> &level_off,
-                const std::vector<uint64_t> &koff, const std::vector<uint8_t> &kfix,
-                const std::vector<uint32_t> &ikey, const std::vector<uint32_t> &usrc,
-                const std::vector<uint8_t> &force, const std::vector<uint64_t> &soff, bool *taken) {
+                bv_event_itx_out *out, bool dag, const std::vector<uint32_t> &order,
+                const std::vector<uint32_t> &level_off, const EvfPrep &p, bool *taken) {
+  const std::vector<uint64_t> &koff = p.koff, &soff = p.soff;
+  const std::vector<uint8_t> &kfix = p.kfix, &force = p.force;
+  const std::vector<uint32_t> &ikey = p.ikey, &usrc = p.usrc;
   const bv_event_batch *eb = &x->events;
   const uint64_t n = eb->n_events, m = x->itx_start ? x->itx_start[n] : 0, N = n + m;
   const uint32_t n_keys = eb->n_keys;
@@ -198,27 +263,52 @@ int small_route(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   return BV_OK;
 }
 
-// f: the same batch with its block signatures as fields (x == &f->ev; checked
-// by the caller, at least one block signature), or null
-int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
-                bv_event_itx_out *out, bool *no_itx) {
-  bv_host_call call;
-  call.t0 = std::chrono::steady_clock::now();
+// What the entries check before anything runs, once over the whole batch (the
+// group's too).  *route: EVF_RUN, or the fall-back the caller takes outside
+// the lock: the batch has no ITX (bv_verify_events_itx) or no block signature
+// (bv_verify_events_fields), and the entry that takes fragments validates it.
+int evf_validate(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, int *route) {
   const bv_event_batch *eb = &x->events;
   const uint64_t n = eb->n_events;
+  *route = EVF_RUN;
   if (eb->itx_off || eb->itx_json)
     return bv_fail(ctx, BV_E_ARGS, "events.itx_off / itx_json must be NULL (the ITXs come from fields)");
   if (n && !eb->sig_text) return bv_fail(ctx, BV_E_ARGS, "events.sig_text is required");
+  if (f) {
+    if (const char *why = check_bsig(f, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
+    if (!n || !f->bsig_start[n]) {
+      *route = EVF_NO_BSIG;
+      return BV_OK;
+    }
+  }
   const bool itx_fields = !f || x->itx_start;  // (a fields batch may carry no ITX fields at all)
   if (itx_fields)
     if (const char *why = check_itx(x, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
-  const uint64_t m = itx_fields ? x->itx_start[n] : 0, N = n + m;
-  if (m == 0 && !f) {  // bv_verify_events over nil / "[]" fragments (the caller, outside the lock): it validates the events
-    *no_itx = true;
+  if (!f && x->itx_start[n] == 0) {
+    *route = EVF_NO_ITX;
     return BV_OK;
   }
-  int rc = bv_validate_events(ctx, eb);
-  if (rc != BV_OK) return rc;
+  return bv_validate_events(ctx, eb);
+}
+
+// (the fields entry asks bv_small_batch's own first question ahead of the bodies small_route builds for it:
+// past small_max only a key-cache context can take the path)
+bool small_candidate(bv_ctx *ctx, const bv_event_fields_batch *f, uint64_t N) {
+  return ctx->small_path && N <= std::max(ctx->small_max, ctx->small_warm_max) &&
+         (!f || N <= ctx->small_max || (ctx->flags & BV_F_KEY_CACHE));
+}
+
+int evf_launch(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, const bv_ev_shard &sh,
+               const EvfPrep &p, const std::vector<uint32_t> *order, const std::vector<uint32_t> *level_off,
+               bv_evf_call *call_p);
+
+// f: the same batch with its block signatures as fields (x == &f->ev; at
+// least one block signature), or null.  The batch is validated (evf_validate).
+int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
+                bv_event_itx_out *out, bv_evf_call &call) {
+  const bv_event_batch *eb = &x->events;
+  const uint64_t n = eb->n_events;
+  const bool itx_fields = !f || x->itx_start;
   hipStream_t st = ctx->stream;
   ctx->timing = bv_timing{};
   ctx->last = st;
@@ -228,68 +318,97 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   const bool dag = memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n) != nullptr;
   if (dag) bv_dag_levels(*eb, order, level_off);
 
-  // the ITX keys: decoded at a fixed stride by the pool, then packed behind
-  // the creators' keys, one slot per DISTINCT key: an ITX whose key equals a
-  // creator's or an earlier ITX's names that slot (a SyncResponse's ITXs are
-  // about a few peers: the batch keeps its per-key tables and key-cache hits)
-  const uint32_t n_keys = eb->n_keys;
-  if ((uint64_t)n_keys + m > 0xFFFFFFFFull) return bv_fail(ctx, BV_E_ARGS, "more than 2^32 keys");
-  const uint64_t ev_key_len = eb->key_off[n_keys];
-  std::vector<uint8_t> kfix(m * kItxKeyMax), klen(m), force(m);
-  if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
-    std::vector<uint8_t> big;
-    for (uint64_t i = lo; i < hi; i++) {
-      const int64_t k = decode_key(x, i, kfix.data() + i * kItxKeyMax, big);
-      force[i] = k < 0;
-      klen[i] = k < 0 ? 0 : (uint8_t)k;
-    }
-    return true;
-  });
-  std::vector<uint64_t> koff(eb->key_off, eb->key_off + n_keys + 1);
-  std::vector<uint32_t> ikey(m), usrc;  // ITX i's key slot; the ITX whose bytes fill slot n_keys + u
-  {
-    std::unordered_map<std::string, uint32_t> slot;
-    for (uint32_t k = 0; k < n_keys; k++)
-      slot.emplace(koff[k + 1] > koff[k] ? std::string((const char *)eb->key_bytes + koff[k], koff[k + 1] - koff[k])
-                                         : std::string(),
-                   k);
-    for (uint64_t i = 0; i < m; i++) {
-      const auto ins = slot.emplace(std::string((const char *)kfix.data() + i * kItxKeyMax, klen[i]),
-                                    (uint32_t)(n_keys + usrc.size()));
-      if (ins.second) {
-        usrc.push_back((uint32_t)i);
-        koff.push_back(koff.back() + klen[i]);
-      }
-      ikey[i] = ins.first->second;
-    }
-  }
-  const uint64_t K = (uint64_t)n_keys + usrc.size();
-  const uint64_t key_len = koff[K];
-
-  // the signature text: the events', then the ITXs' Signature strings
-  const uint64_t ev_text_len = eb->sig_off[n];
-  std::vector<uint64_t> soff(N + 1);
-  memcpy(soff.data(), eb->sig_off, (n + 1) * 8);
-  for (uint64_t i = 0; i < m; i++) soff[n + i + 1] = soff[n + i] + itx_str_len(*x, i, ITX_SIGNATURE);
-  const uint64_t text_len = soff[N];
-
-  // (the fields entry asks bv_small_batch's own first question ahead of the bodies small_route builds for it:
-  // past small_max only a key-cache context can take the path)
-  if (ctx->small_path && N <= std::max(ctx->small_max, ctx->small_warm_max) &&
-      (!f || N <= ctx->small_max || (ctx->flags & BV_F_KEY_CACHE))) {
+  EvfPrep p;
+  int rc = evf_prep(ctx, x, itx_fields, 0, n, p);
+  if (rc != BV_OK) return rc;
+  if (small_candidate(ctx, f, n + p.m)) {
     bool taken = false;
-    rc = small_route(ctx, x, f, res, out, dag, order, level_off, koff, kfix, ikey, usrc, force, soff, &taken);
+    rc = small_route(ctx, x, f, res, out, dag, order, level_off, p, &taken);
     if (rc != BV_OK || taken) return rc;
   }
+  // the bulk pipeline over the whole batch as one range with zero bases
+  const bv_ev_shard whole{0, n, 0, eb->parent_hashes ? eb->n_parent_hashes : 0};
+  rc = evf_launch(ctx, x, f, whole, p, dag ? &order : nullptr, &level_off, &call);
+  if (rc != BV_OK) return rc;
+  rc = bv_mark_done(ctx, st);
+  if (rc != BV_OK) return rc;
+  return bv_evf_finish(ctx, res, out, &call, true);
+}
+
+// The bulk pipeline over events [sh.a, sh.z) of a validated batch and the ITXs
+// they own: everything up to the call's last enqueued command (the caller
+// records the end with bv_mark_done and collects with bv_evf_finish), as
+// bv_events_launch.  The single-context entries pass the whole batch (order:
+// its in-batch DAG, if it has one); the group one shard per slot.  The range's
+// slices are staged from where they lie in the caller's arrays and the values
+// in them stay the whole batch's: the device subtracts the bases (EvjBases,
+// ItxBases, BsigBases).  With every base zero the un-based kernels run.
+int evf_launch(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, const bv_ev_shard &sh,
+               const EvfPrep &p, const std::vector<uint32_t> *order, const std::vector<uint32_t> *level_off,
+               bv_evf_call *call_p) {
+  bv_host_call &call = call_p->host;
+  int rc = BV_OK;
+  hipStream_t st = ctx->stream;
+  const uint64_t a = sh.a, n = sh.z - sh.a;  // the range's events: e below is range-local
+  if (n == 0) return BV_OK;                  // (an empty shard launches nothing)
+  const bv_event_batch whole_events = x->events;
+  const bool itx_fields = !f || x->itx_start;
+  const bool dag = order != nullptr;
+  const uint64_t i0 = p.i0, m = p.m, N = n + m;
+  call_p->n = n, call_p->m = m;
+  const std::vector<uint64_t> &koff = p.koff, &soff = p.soff;
+  const std::vector<uint8_t> &kfix = p.kfix, &force = p.force;
+  const std::vector<uint32_t> &ikey = p.ikey, &usrc = p.usrc;
+  const uint32_t n_keys = whole_events.n_keys;
+  const uint64_t ev_key_len = whole_events.key_off[n_keys];
+  const uint64_t K = (uint64_t)n_keys + usrc.size();
+  const uint64_t key_len = koff[K];
+  const uint64_t ev_text_len = soff[n], text_len = soff[N];
+
+  // the bases, and the range's view of the caller's arrays (host pointers to its first elements)
+  const uint64_t j0 = f ? f->bsig_start[a] : 0, nb = f ? f->bsig_start[sh.z] - j0 : 0;  // block signatures, as fields
+  const bool bv_bytes = f && f->bsig_val_kind && nb && memchr(f->bsig_val_kind + j0, BV_BSIG_VAL_BYTES, nb);
+  EvjBases bs = {};
+  bs.ev = a;
+  bs.tx = whole_events.tx_start[a];
+  bs.txb = whole_events.tx_start[whole_events.n_events] ? whole_events.tx_off[bs.tx] : 0;
+  bs.bsig = whole_events.bsig_off ? whole_events.bsig_off[a] : 0;
+  bs.ph = sh.hash_lo;
+  const ItxBases ib{i0, m ? x->itx_str_off[4 * i0] : 0};
+  const BsigBases sb{j0, nb ? f->bsig_sig_off[j0] : 0, bv_bytes ? f->bsig_val_off[j0] : 0};
+  const bool rebased = bs.ev || bs.tx || bs.txb || bs.bsig || bs.ph || ib.itx || ib.str || sb.bsig || sb.sig || sb.val;
+  bv_event_itx_batch xv = *x;
+  bv_event_fields_batch fv = {};
+  if (f) fv = *f;
+  {
+    auto adv = [](auto *&q, uint64_t k) {
+      if (q) q += k;
+    };
+    bv_event_batch &v = xv.events;
+    v.n_events = n;
+    adv(v.creator, a), adv(v.index, a), adv(v.timestamp, a);
+    adv(v.parent_kind, 2 * a), adv(v.parent_ref, 2 * a);
+    adv(v.parent_hashes, 32 * sh.hash_lo);
+    adv(v.tx_start, a), adv(v.tx_off, bs.tx), adv(v.tx_bytes, bs.txb);
+    adv(v.tx_list_nil, a), adv(v.tx_nil, bs.tx);
+    adv(v.bsig_off, a), adv(v.bsig_json, bs.bsig);
+    adv(v.sig_text, v.sig_off[a]);
+    adv(xv.itx_start, a), adv(xv.itx_list_nil, a), adv(xv.itx_type, i0);
+    adv(xv.itx_str_off, 4 * i0), adv(xv.itx_str, ib.str);
+    adv(fv.bsig_start, a), adv(fv.bsig_list_nil, a), adv(fv.bsig_index, j0), adv(fv.bsig_sig_off, j0);
+    adv(fv.bsig_sig, sb.sig), adv(fv.bsig_val_kind, j0), adv(fv.bsig_val_off, j0), adv(fv.bsig_val_bytes, sb.val);
+  }
+  const bv_event_batch *eb = &xv.events;  // (its values are the whole batch's: subtract the bases)
+  const bv_event_itx_batch *xs = &xv;
+  const bv_event_fields_batch *fs = f ? &fv : nullptr;
 
   // staging layout (pinned host and HBM)
-  const uint64_t n_tx = eb->tx_start[n], tx_len = n_tx ? eb->tx_off[n_tx] : 0;
-  const uint64_t bsig_len = eb->bsig_off ? eb->bsig_off[n] : 0;
-  const uint64_t str_len = m ? x->itx_str_off[4 * m] : 0;
-  const uint64_t nb = f ? f->bsig_start[n] : 0, bs_len = nb ? f->bsig_sig_off[nb] : 0;  // block signatures, as fields
-  const bool bv_bytes = f && bsig_has_bytes(f, nb);
-  const uint64_t bv_len = bv_bytes ? f->bsig_val_off[nb] : 0;
-  const uint64_t n_ph = eb->parent_hashes ? eb->n_parent_hashes : 0;
+  const uint64_t n_tx = eb->tx_start[n] - bs.tx, tx_len = n_tx ? eb->tx_off[n_tx] - bs.txb : 0;
+  const uint64_t bsig_len = eb->bsig_off ? eb->bsig_off[n] - bs.bsig : 0;
+  const uint64_t str_len = m ? xs->itx_str_off[4 * m] - ib.str : 0;
+  const uint64_t bs_len = nb ? fs->bsig_sig_off[nb] - sb.sig : 0;
+  const uint64_t bv_len = bv_bytes ? fs->bsig_val_off[nb] - sb.val : 0;
+  const uint64_t n_ph = eb->parent_hashes ? sh.hash_hi - sh.hash_lo : 0;
   // The fields entry's bulk route, a batch of more than one chunk of events:
   // the arrays that are indexed by event (or by an event's transactions or
   // block signatures) cross in event-range slices, chunk by chunk, into the
@@ -303,22 +422,22 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   // bv_verify_events does), and the staging runs around it and around the
   // sliced arrays cross as one copy each.  The ITX entry stages everything.
   StagePlan plan({f ? (size_t)256 << 10 : StagePolicy::kNever, true});
-  plan.space[S_TX] = {eb->tx_start, 0};
-  plan.space[S_BS] = {f ? f->bsig_start : nullptr, 0};
+  plan.space[S_TX] = {eb->tx_start, bs.tx};
+  plan.space[S_BS] = {f ? fs->bsig_start : nullptr, sb.bsig};
   const auto sl = [chunked](StageKind k) { return chunked ? k : StageKind{}; };  // sliced only on that route
   const StageKind k_ev = sl({S_ELEM, S_EV}), k_ev1 = sl({S_OFFS, S_EV}), k_tx = sl({S_ELEM, S_TX}), k_tx1 = sl({S_OFFS, S_TX});
-  const StageKind k_bs = sl({S_ELEM, S_BS}), k_bs1 = sl({S_OFFS, S_BS}), k_txb = sl({S_BYTES, S_TX, eb->tx_off});
-  const StageKind k_bsb = sl({S_BYTES, S_BS, f ? f->bsig_sig_off : nullptr}),
-                  k_bvb = sl({S_BYTES, S_BS, f ? f->bsig_val_off : nullptr});
+  const StageKind k_bs = sl({S_ELEM, S_BS}), k_bs1 = sl({S_OFFS, S_BS}), k_txb = sl({S_BYTES, S_TX, eb->tx_off, bs.txb});
+  const StageKind k_bsb = sl({S_BYTES, S_BS, f ? fs->bsig_sig_off : nullptr, sb.sig}),
+                  k_bvb = sl({S_BYTES, S_BS, f ? fs->bsig_val_off : nullptr, sb.val});
   // (reserve: bytes the driver fills by hand, or that only the device writes)
   const size_t o_koff = plan.add(koff.data(), (K + 1) * 8), o_kb = plan.reserve(key_len, 64), keys_end = plan.total;
   const size_t o_soff = plan.add(soff.data(), (N + 1) * 8);  // the events' text, then the ITXs' (by hand) and the pad
   const size_t o_text = plan.add(eb->sig_text, ev_text_len, {}, 1, text_len - ev_text_len + 64), s_end = plan.total;
   const size_t o_ik = plan.reserve(N * 4);
-  const size_t o_is = itx_fields ? plan.add(x->itx_start, (n + 1) * 8, k_ev1, 8) : plan.reserve((n + 1) * 8);
-  const size_t o_iln = plan.add(x->itx_list_nil, n, k_ev, 1), o_ity = plan.add(x->itx_type, m);
-  const size_t o_iso = m ? plan.add(x->itx_str_off, (4 * m + 1) * 8) : plan.reserve(8);
-  const size_t o_istr = plan.add(x->itx_str, str_len, {}, 1, 64), o_force = plan.add(force.data(), m);
+  const size_t o_is = itx_fields ? plan.add(xs->itx_start, (n + 1) * 8, k_ev1, 8) : plan.reserve((n + 1) * 8);
+  const size_t o_iln = plan.add(xs->itx_list_nil, n, k_ev, 1), o_ity = plan.add(xs->itx_type, m);
+  const size_t o_iso = m ? plan.add(xs->itx_str_off, (4 * m + 1) * 8) : plan.reserve(8);
+  const size_t o_istr = plan.add(xs->itx_str, str_len, {}, 1, 64), o_force = plan.add(force.data(), m);
   const bool bulk = !dag;  // the event fields cross only when the device builds the bodies
   const size_t o_ix = plan.add(eb->index, bulk ? n * 8 : 0, k_ev, 8), o_ts = plan.add(eb->timestamp, bulk ? n * 8 : 0, k_ev, 8);
   const size_t o_pk = plan.add(eb->parent_kind, bulk ? n * 2 : 0, k_ev, 2);
@@ -330,7 +449,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   const size_t o_tln = plan.add(eb->tx_list_nil, bulk ? n : 0, k_ev, 1), o_txn = plan.add(eb->tx_nil, bulk ? n_tx : 0, k_tx, 1);
   const size_t o_bo = plan.add(eb->bsig_off, bulk ? (n + 1) * 8 : 0), o_bj = plan.add(eb->bsig_json, bulk ? bsig_len : 0);
   const bool bf = bulk && f;
-  const bv_event_fields_batch none = {}, &g = bf ? *f : none;  // (no block-signature field crosses otherwise)
+  const bv_event_fields_batch none = {}, &g = bf ? *fs : none;  // (no block-signature field crosses otherwise)
   // an array whose place does not depend on its presence: the bytes are reserved when it is absent
   const auto fld = [&](const void *src, size_t bytes, StageKind k, size_t unit, size_t pad = 0) {
     return src ? plan.add(src, bf ? bytes : 0, k, unit, pad) : plan.reserve(bf ? bytes : 0, pad);
@@ -357,13 +476,13 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   HIPCHK(hipEventRecord(ev[E_CALL], cs), BV_E_LAUNCH, "event");
   plan.mark_direct(bv_is_pinned);
   // each phase as one piece: the planned arrays into the staging block, then the copies in layout order
-  auto h2d = [&](size_t a, size_t z) { return bv_stage_range(ctx, plan, a, z, z - a); };
+  auto h2d = [&](size_t b0, size_t b1) { return bv_stage_range(ctx, plan, b0, b1, b1 - b0); };
 
   // the keys
   if (ev_key_len) memcpy(pin + o_kb, eb->key_bytes, ev_key_len);  // (always staged: the key cache reads them here)
   for (size_t u = 0; u < usrc.size(); u++) {
-    const uint64_t a = koff[n_keys + u], len = koff[n_keys + u + 1] - a;
-    if (len) memcpy(pin + o_kb + a, kfix.data() + (size_t)usrc[u] * kItxKeyMax, len);
+    const uint64_t ka = koff[n_keys + u], len = koff[n_keys + u + 1] - ka;
+    if (len) memcpy(pin + o_kb + ka, kfix.data() + (size_t)usrc[u] * kItxKeyMax, len);
   }
   memset(pin + o_kb + key_len, 0, 64);
   if ((rc = h2d(0, keys_end)) != BV_OK) return rc;
@@ -392,7 +511,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   if (m) par(ctx->pool, m, 4096, [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; i++) {
       const uint64_t len = soff[n + i + 1] - soff[n + i];
-      if (len) memcpy(pin + o_text + soff[n + i], itx_str_ptr(*x, i, ITX_SIGNATURE), len);
+      if (len) memcpy(pin + o_text + soff[n + i], itx_str_ptr(*x, i0 + i, ITX_SIGNATURE), len);
     }
     return true;
   });
@@ -464,25 +583,32 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   rc = bv_out_bufs(ctx, &vb, nullptr, nullptr, nullptr, true, &pipe.o);
   if (rc != BV_OK) return rc;
   uint32_t *dig = pipe.o.dig;
-  HIPCHK(bvk::itx_body_hash(st, dx, m, n, dig), BV_E_LAUNCH, "k_itx_body_hash");
+  // events [c0, c1) of the range: the batch's [a + c0, a + c1) to a rebased kernel
+  const auto hash_fields = [&](uint64_t c0, uint64_t c1) {
+    return rebased ? bvk::ev_body_hash_fields_rb(st, df, a + c0, a + c1, bs, ib, sb, dig)
+                   : bvk::ev_body_hash_fields(st, df, c0, c1, dig);
+  };
+  HIPCHK(rebased ? bvk::itx_body_hash_rb(st, dx, m, n, ib, dig) : bvk::itx_body_hash(st, dx, m, n, dig), BV_E_LAUNCH,
+         "k_itx_body_hash");
   if (chunked) {
-    for (uint64_t a = 0; a < n; a += chunk_ev) {
-      const uint64_t z = std::min(n, a + chunk_ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += chunk_ev) {
+      const uint64_t c1 = std::min(n, c0 + chunk_ev);
       // pinned arrays' slices by DMA from where they lie, the rest into pinned memory, then its DMA
-      if ((rc = bv_stage_slices(ctx, plan, a, z)) != BV_OK) return rc;
-      hipEvent_t landed = ctx->chunk_ev[(a / chunk_ev) % ctx->chunk_ev.size()];
+      if ((rc = bv_stage_slices(ctx, plan, c0, c1)) != BV_OK) return rc;
+      hipEvent_t landed = ctx->chunk_ev[(c0 / chunk_ev) % ctx->chunk_ev.size()];
       HIPCHK(hipEventRecord(landed, cs), BV_E_LAUNCH, "event");
       HIPCHK(hipStreamWaitEvent(st, landed, 0), BV_E_LAUNCH, "join chunk");
-      HIPCHK(bvk::ev_body_hash_fields(st, df, a, z, dig), BV_E_LAUNCH, "k_ev_body_hash_fields");
-      if (z < n && (rc = pipe.upto(z)) != BV_OK) return rc;  // (the last chunk's items: pipe.finish below)
+      HIPCHK(hash_fields(c0, c1), BV_E_LAUNCH, "k_ev_body_hash_fields");
+      if (c1 < n && (rc = pipe.upto(c1)) != BV_OK) return rc;  // (the last chunk's items: pipe.finish below)
     }
   } else if (bf) {
-    HIPCHK(bvk::ev_body_hash_fields(st, df, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_fields");
+    HIPCHK(hash_fields(0, n), BV_E_LAUNCH, "k_ev_body_hash_fields");
   } else if (bulk) {
-    HIPCHK(bvk::ev_body_hash_itx(st, dx, 0, n, dig), BV_E_LAUNCH, "k_ev_body_hash_itx");
+    HIPCHK(rebased ? bvk::ev_body_hash_itx_rb(st, dx, a, a + n, bs, ib, dig) : bvk::ev_body_hash_itx(st, dx, 0, n, dig),
+           BV_E_LAUNCH, "k_ev_body_hash_itx");
   } else {
     // the host's part, beside the device's key / s^-1 work and the ITX hashing
-    dag_hash(x, f, order, level_off, bv_pool_parfor(ctx), ctx->dag_scratch, pin + o_dig);
+    dag_hash(x, f, *order, *level_off, bv_pool_parfor(ctx), ctx->dag_scratch, pin + o_dig);
     HIPCHK(hipMemcpyAsync(dig, pin + o_dig, n * 32, hipMemcpyHostToDevice, cs), BV_E_LAUNCH, "h2d digests");
   }
   HIPCHK(hipEventRecord(ev[E_STAGED], cs), BV_E_LAUNCH, "event");
@@ -492,9 +618,13 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   HIPCHK(hipEventRecord(ev[E_HASHED], st), BV_E_LAUNCH, "event");
   rc = pipe.finish();  // every item: the events' and the ITXs'
   if (rc != BV_OK) return rc;
-  HIPCHK(bvk::ev_compose(st, n, (const uint64_t *)(dev + o_is), pipe.o.status, dev + o_force, dev + o_evst, (uint32_t *)(dev + o_dby),
-                         (uint64_t *)(dev + o_bits), dev + o_ist),
+  const uint64_t *d_is = (const uint64_t *)(dev + o_is);
+  HIPCHK(ib.itx ? bvk::ev_compose_rb(st, n, d_is, ib.itx, pipe.o.status, dev + o_force, dev + o_evst,
+                                     (uint32_t *)(dev + o_dby), (uint64_t *)(dev + o_bits), dev + o_ist)
+                : bvk::ev_compose(st, n, d_is, pipe.o.status, dev + o_force, dev + o_evst, (uint32_t *)(dev + o_dby),
+                                  (uint64_t *)(dev + o_bits), dev + o_ist),
          BV_E_LAUNCH, "k_ev_compose");
+  call_p->d_bits = dev + o_bits;
 
   // results: the digests (events, then ITXs), then k_ev_compose's outputs as they lie in HBM, in one copy
   const size_t p_st = align256(N * 32), p_bits = p_st + (o_bits - o_evst), p_dby = p_st + (o_dby - o_evst),
@@ -508,18 +638,7 @@ int verify_impl(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_
   HIPCHK(hipMemcpyAsync(pout + p_st, dev + o_evst, fold_len, hipMemcpyDeviceToHost, st), BV_E_LAUNCH,
          "d2h statuses, bits, decided_by");
   HIPCHK(hipEventRecord(ev[E_OUT], st), BV_E_LAUNCH, "event");
-  rc = bv_mark_done(ctx, st);
-  if (rc != BV_OK) return rc;
-  bv_batch sizes = {};
-  sizes.n_msgs = n;
-  sizes.n_items = n;
-  rc = bv_host_finish(ctx, &sizes, res, &call, true);
-  if (rc != BV_OK) return rc;
-  if (out) {
-    if (out->itx_hash && m) memcpy(out->itx_hash, pout + n * 32, m * 32);
-    if (out->itx_status && m) memcpy(out->itx_status, pout + p_ist, m);
-    if (out->decided_by) memcpy(out->decided_by, pout + p_dby, n * 4);
-  }
+  call_p->p_ist = p_ist, call_p->p_dby = p_dby;
   return BV_OK;
 }
 
@@ -529,18 +648,57 @@ void lens_scan(uint64_t n, uint64_t *off) {
 
 }  // namespace
 
-extern "C" int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out) {
-  if (!ctx || !x || !res) return BV_E_ARGS;
-  bool no_itx = false;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
-    const int rc = verify_impl(ctx, x, nullptr, res, out, &no_itx);
-    if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
-    if (!no_itx) return BV_OK;
+int bv_evf_finish(bv_ctx *ctx, bv_result *res, bv_event_itx_out *out, bv_evf_call *call, bool bits_out) {
+  const uint64_t n = call->n, m = call->m;
+  bv_batch sizes = {};
+  sizes.n_msgs = n;
+  sizes.n_items = n;
+  const int rc = bv_host_finish(ctx, &sizes, res, &call->host, bits_out);
+  if (rc != BV_OK) return rc;
+  const uint8_t *pout = call->host.pout;
+  if (out) {
+    if (out->itx_hash && m) memcpy(out->itx_hash, pout + n * 32, m * 32);
+    if (out->itx_status && m) memcpy(out->itx_status, pout + call->p_ist, m);
+    if (out->decided_by) memcpy(out->decided_by, pout + call->p_dby, n * 4);
   }
-  // no ITX at all: bv_verify_events over the same events, a nil list as the
-  // empty fragment (null) and an empty non-nil one as "[]"
+  return BV_OK;
+}
+
+int bv_evf_validate(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, int *route) {
+  return evf_validate(ctx, x, f, route);
+}
+
+// (A candidate batch is prepared whole here, and again shard by shard when
+// small_route declines it: a second pass over at most small_warm_max items.)
+int bv_evf_try_small(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
+                     bv_event_itx_out *out, bool *taken) {
+  const uint64_t n = x->events.n_events;
+  const bool itx_fields = !f || x->itx_start;
+  *taken = false;
+  if (!small_candidate(ctx, f, n + (itx_fields ? x->itx_start[n] : 0))) return BV_OK;
+  ctx->timing = bv_timing{};
+  ctx->last = ctx->stream;
+  EvfPrep p;
+  const int rc = evf_prep(ctx, x, itx_fields, 0, n, p);
+  if (rc != BV_OK) return rc;
+  return small_route(ctx, x, f, res, out, false, {}, {}, p, taken);
+}
+
+int bv_evf_launch(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, const bv_ev_shard &sh,
+                  bv_evf_call *call) {
+  ctx->timing = bv_timing{};
+  ctx->last = ctx->stream;
+  if (sh.z == sh.a) return BV_OK;
+  EvfPrep p;  // the shard's ITX keys and signature text, on this ctx's pool
+  const int rc = evf_prep(ctx, x, !f || x->itx_start, sh.a, sh.z, p);
+  return rc == BV_OK ? evf_launch(ctx, x, f, sh, p, nullptr, nullptr, call) : rc;
+}
+
+// A batch without ITXs through the entry that takes fragments (`verify_events`:
+// bv_verify_events, or the group's): a nil list as the empty fragment (null)
+// and an empty non-nil one as "[]"
+int bv_evf_no_itx(const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out,
+                  const std::function<int(const bv_event_batch *, bv_result *)> &verify_events) {
   bv_event_batch evb = x->events;
   const uint64_t n = evb.n_events;
   std::vector<uint64_t> frag_off;
@@ -555,9 +713,26 @@ extern "C" int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *x, bv
     evb.itx_off = frag_off.data();
     evb.itx_json = frag.data();
   }
-  const int rc = bv_verify_events(ctx, &evb, res);
+  const int rc = verify_events(&evb, res);
   if (rc == BV_OK && out && out->decided_by) memset(out->decided_by, 0xFF, n * 4);  // BV_EV_SELF
   return rc;
+}
+
+extern "C" int bv_verify_events_itx(bv_ctx *ctx, const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out) {
+  if (!ctx || !x || !res) return BV_E_ARGS;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
+    bv_evf_call call;
+    call.host.t0 = std::chrono::steady_clock::now();
+    int route = EVF_RUN;
+    int rc = evf_validate(ctx, x, nullptr, &route);
+    if (rc == BV_OK && route == EVF_RUN) rc = verify_impl(ctx, x, nullptr, res, out, call);
+    if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
+    if (route == EVF_RUN) return BV_OK;
+  }
+  // no ITX at all: bv_verify_events over the same events
+  return bv_evf_no_itx(x, res, out, [ctx](const bv_event_batch *eb, bv_result *r) { return bv_verify_events(ctx, eb, r); });
 }
 
 extern "C" int bv_itx_body_lens(const bv_event_itx_batch *x, uint64_t *off) {
@@ -623,35 +798,43 @@ static void empty_list_fragments(uint64_t n, const uint8_t *nil, bool null_is_ni
   *j = json.data();
 }
 
-extern "C" int bv_verify_events_fields(bv_ctx *ctx, const bv_event_fields_batch *f, bv_result *res,
-                                       bv_event_itx_out *out) {
-  if (!ctx || !f || !res) return BV_E_ARGS;
-  const bv_event_batch *eb = &f->ev.events;
-  const uint64_t n = eb->n_events;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
-    if (eb->itx_off || eb->itx_json)
-      return bv_fail(ctx, BV_E_ARGS, "events.itx_off / itx_json must be NULL (the ITXs come from fields)");
-    if (n && !eb->sig_text) return bv_fail(ctx, BV_E_ARGS, "events.sig_text is required");
-    if (const char *why = check_bsig(f, ctx->pool)) return bv_fail(ctx, BV_E_ARGS, why);
-    if (n && f->bsig_start[n]) {
-      bool unused = false;
-      const int rc = verify_impl(ctx, &f->ev, f, res, out, &unused);
-      return rc == BV_OK ? BV_OK : bv_drain(ctx, ctx->stream, rc);
-    }
-  }
-  // no block signature at all: the entry that takes fragments, over the same
-  // events with nil / "[]" fragments
+// A fields batch without block signatures through the entry that takes
+// fragments, over the same events with nil / "[]" fragments (`verify_itx`,
+// `verify_events`: bv_verify_events_itx and bv_verify_events, or the group's)
+int bv_evf_no_bsig(const bv_event_fields_batch *f, bv_result *res, bv_event_itx_out *out,
+                   const std::function<int(const bv_event_itx_batch *, bv_result *, bv_event_itx_out *)> &verify_itx,
+                   const std::function<int(const bv_event_batch *, bv_result *)> &verify_events) {
+  const uint64_t n = f->ev.events.n_events;
   std::vector<uint64_t> boff, ioff;
   std::vector<uint8_t> bjson, ijson;
   bv_event_itx_batch xi = f->ev;
   empty_list_fragments(n, f->bsig_list_nil, false, boff, bjson, &xi.events.bsig_off, &xi.events.bsig_json);
-  if (xi.itx_start) return bv_verify_events_itx(ctx, &xi, res, out);
+  if (xi.itx_start) return verify_itx(&xi, res, out);
   empty_list_fragments(n, f->ev.itx_list_nil, true, ioff, ijson, &xi.events.itx_off, &xi.events.itx_json);
-  const int rc = bv_verify_events(ctx, &xi.events, res);
+  const int rc = verify_events(&xi.events, res);
   if (rc == BV_OK && out && out->decided_by) memset(out->decided_by, 0xFF, n * 4);  // BV_EV_SELF
   return rc;
+}
+
+extern "C" int bv_verify_events_fields(bv_ctx *ctx, const bv_event_fields_batch *f, bv_result *res,
+                                       bv_event_itx_out *out) {
+  if (!ctx || !f || !res) return BV_E_ARGS;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device), BV_E_NODEVICE, "hipSetDevice");
+    bv_evf_call call;
+    call.host.t0 = std::chrono::steady_clock::now();
+    int route = EVF_RUN;
+    int rc = evf_validate(ctx, &f->ev, f, &route);
+    if (rc == BV_OK && route == EVF_RUN) rc = verify_impl(ctx, &f->ev, f, res, out, call);
+    if (rc != BV_OK) return bv_drain(ctx, ctx->stream, rc);
+    if (route == EVF_RUN) return BV_OK;
+  }
+  // no block signature at all: the entry that takes fragments
+  return bv_evf_no_bsig(
+      f, res, out,
+      [ctx](const bv_event_itx_batch *xi, bv_result *r, bv_event_itx_out *o) { return bv_verify_events_itx(ctx, xi, r, o); },
+      [ctx](const bv_event_batch *eb, bv_result *r) { return bv_verify_events(ctx, eb, r); });
 }
 
 // The fields the serialiser reads, without a context

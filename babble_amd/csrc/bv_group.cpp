@@ -23,10 +23,11 @@
 // multi-device code path, so it runs on hardware with one GPU
 // (tests/test_gpu_cache_group.py::test_group_logical_shards).
 //
-// Three entries share the gather tail (gather_and_finish):
+// Every entry shares the gather tail (gather_and_finish):
 // bv_group_verify_batch (serialized bodies, above), bv_group_verify_events
-// (wire fields, sharded by event index) and bv_group_verify_blocks (block
-// fields, sharded by block; both below).
+// (wire fields, sharded by event index), bv_group_verify_events_itx /
+// bv_group_verify_events_fields (the one-call event entries, sharded the same
+// way) and bv_group_verify_blocks (block fields, sharded by block; all below).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -192,7 +193,7 @@ extern "C" int bv_group_get_timing(const bv_group *g, int i, bv_timing *out) {
 }
 
 static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPlan &p);
-static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items);
+static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items, const void *src);
 static int gather_and_finish(bv_group *g, uint64_t words, std::vector<uint64_t> &gathered,
                              const std::function<int(int, bv_ctx *)> &finish);
 
@@ -286,7 +287,7 @@ static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPla
       rcs[d] = bv_host_launch(c, &sb[d], &calls[d], &sr);
       if (rcs[d] != BV_OK) return;
       // the shard's bits, zero-padded to `words`, as the all-gather send buffer
-      rcs[d] = stage_shard_bits(g, d, words, sb[d].n_items);
+      rcs[d] = stage_shard_bits(g, d, words, sb[d].n_items, c->S().bits.p);
     });
   for (auto &t : th) t.join();
   for (int d = 0; d < D; d++)
@@ -324,16 +325,18 @@ static int group_verify(bv_group *g, const bv_batch *b, bv_result *res, GroupPla
   return BV_OK;
 }
 
-// A shard's accept bits (`n_items` of them, in its ctx's slot; none for an
-// empty shard), zero-padded to `words`, as the gather's send buffer on its
-// ctx's stream.  Called with the ctx locked and its device current.
-static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items) {
+// A shard's accept bits (`n_items` of them at `src` on its device: its ctx's
+// slot, or for the entries that fold, k_ev_compose's words in the staging
+// block; none for an empty shard), zero-padded to `words`, as the gather's
+// send buffer on its ctx's stream.  Called with the ctx locked and its device
+// current.
+static int stage_shard_bits(bv_group *g, int d, uint64_t words, uint64_t n_items, const void *src) {
   bv_ctx *c = g->ctx[d];
   const int D = (int)g->ctx.size();
   if (g->send[d].ensure(words * 8) != hipSuccess || g->recv[d].ensure(words * 8 * D) != hipSuccess) return BV_E_OOM;
   const uint64_t sw = (n_items + 63) / 64;
   if (hipMemsetAsync(g->send[d].p, 0, words * 8, c->stream) != hipSuccess ||
-      (sw && hipMemcpyAsync(g->send[d].p, c->S().bits.p, sw * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
+      (sw && hipMemcpyAsync(g->send[d].p, src, sw * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
       hipEventRecord(g->sent[d], c->stream) != hipSuccess)
     return BV_E_LAUNCH;
   return BV_OK;
@@ -446,7 +449,7 @@ static int group_verify_events(bv_group *g, const bv_event_batch *eb, bv_result 
       if (!sh.hash_hi) sh.hash_lo = 0;
       const bv_result sr = shard_res(d);
       rcs[d] = bv_events_launch(c, eb, sh, &sr, &calls[d]);
-      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.z - sh.a);
+      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.z - sh.a, c->S().bits.p);
     });
   for (auto &t : th) t.join();
   for (int d = 0; d < D; d++)
@@ -477,6 +480,137 @@ extern "C" int bv_group_verify_events(bv_group *g, const bv_event_batch *eb, bv_
   if (!g || !eb || !res) return BV_E_ARGS;
   std::lock_guard<std::mutex> lk(g->mu);
   const int rc = group_verify_events(g, eb, res);
+  if (rc != BV_OK) drain_all(g, rc);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// bv_group_verify_events_itx / bv_group_verify_events_fields: the one-call
+// entries (bv_verify_events_itx, bv_verify_events_fields; `f` null for the
+// former) sharded by event index at bv_plan_event_shards' bounds.  A shard
+// owns its events' ITXs, block signatures and transactions; its items are its
+// events followed by its ITXs.  Every slot stages its shard's slices of the
+// caller's arrays as they are and the device subtracts the shard's bases
+// (bv_evf_launch; EvjBases, ItxBases, BsigBases).  Digests, statuses,
+// decided_by and the ITX outputs come back per slot; only the accept bits
+// (k_ev_compose's words) go through the gather.  A batch with in-batch
+// parents, or one the single-context entry runs on its one-launch small path,
+// is one single-context call on slot 0.
+// ---------------------------------------------------------------------------
+static int group_verify_events_fields(bv_group *g, const bv_event_itx_batch *x, const bv_event_fields_batch *f,
+                                      bv_result *res, bv_event_itx_out *out) {
+  const int D = (int)g->ctx.size();
+  const bv_event_batch *eb = &x->events;
+  const uint64_t n = eb->n_events;
+  bv_ctx *c0 = g->ctx[0];
+  int route = EVF_RUN;
+  {
+    std::lock_guard<std::mutex> clk(c0->mu);
+    const int rc = bv_evf_validate(c0, x, f, &route);
+    if (rc != BV_OK) return gfail(g, rc, c0->err);
+  }
+  // the fall-back equalities of the single-context entries, through the group
+  const auto g_events = [g](const bv_event_batch *e, bv_result *r) { return group_verify_events(g, e, r); };
+  if (route == EVF_NO_ITX) return bv_evf_no_itx(x, res, out, g_events);
+  if (route == EVF_NO_BSIG)
+    return bv_evf_no_bsig(
+        f, res, out,
+        [g](const bv_event_itx_batch *xi, bv_result *r, bv_event_itx_out *o) {
+          return group_verify_events_fields(g, xi, nullptr, r, o);
+        },
+        g_events);
+  if (memchr(eb->parent_kind, BV_PARENT_EVENT, 2 * n)) {  // a SyncResponse DAG: whole, on slot 0
+    const int rc = f ? bv_verify_events_fields(c0, f, res, out) : bv_verify_events_itx(c0, x, res, out);
+    return rc == BV_OK ? rc : gfail(g, rc, c0->err);
+  }
+  {
+    std::lock_guard<std::mutex> clk(c0->mu);
+    if (hipSetDevice(c0->device) != hipSuccess) return gfail(g, BV_E_NODEVICE, "hipSetDevice");
+    bool taken = false;
+    const int rc = bv_evf_try_small(c0, x, f, res, out, &taken);
+    if (rc != BV_OK) return gfail(g, rc, c0->err);
+    if (taken) return BV_OK;
+  }
+  std::vector<uint64_t> bounds(D + 1);
+  plan_event_bounds(n, D, false, bounds.data());
+  uint64_t words = 1;
+  for (int d = 0; d < D; d++) words = std::max<uint64_t>(words, (bounds[d + 1] - bounds[d] + 63) / 64);
+
+  // stage, build, hash, verify and fold every shard concurrently (one host
+  // thread per slot); every result but the accept bits goes straight to the
+  // shard's part of the caller's buffers
+  const uint64_t *is = x->itx_start;  // (NULL: a fields batch without ITX fields)
+  auto shard_res = [&](int d) {
+    bv_result sr = {};
+    sr.msg_hash = res->msg_hash ? res->msg_hash + 32 * bounds[d] : nullptr;
+    sr.status = res->status ? res->status + bounds[d] : nullptr;
+    return sr;  // (no accept_bits: the shard's bits leave through the gather)
+  };
+  auto shard_out = [&](int d) {
+    bv_event_itx_out so = {};
+    if (!out) return so;
+    const uint64_t i0 = is ? is[bounds[d]] : 0;
+    so.itx_hash = out->itx_hash ? out->itx_hash + 32 * i0 : nullptr;
+    so.itx_status = out->itx_status ? out->itx_status + i0 : nullptr;
+    so.decided_by = out->decided_by ? out->decided_by + bounds[d] : nullptr;
+    return so;
+  };
+  std::vector<bv_evf_call> calls(D);
+  std::vector<int> rcs(D, BV_OK);
+  std::vector<std::thread> th;
+  for (int d = 0; d < D; d++)
+    th.emplace_back([&, d]() {
+      bv_ctx *c = g->ctx[d];
+      std::lock_guard<std::mutex> clk(c->mu);
+      if (hipSetDevice(c->device) != hipSuccess) {
+        rcs[d] = BV_E_NODEVICE;
+        return;
+      }
+      calls[d].host.t0 = std::chrono::steady_clock::now();
+      bv_ev_shard sh{bounds[d], bounds[d + 1], UINT64_MAX, 0};
+      std::mutex rmu;
+      c->pool->parallel_for(sh.z - sh.a, 1 << 16, [&](uint64_t p0, uint64_t p1) {
+        uint64_t lo = 0, hi = 0;
+        (void)event_hash_range(eb, sh.a + p0, sh.a + p1, &lo, &hi);  // (the batch is validated)
+        std::lock_guard<std::mutex> lk(rmu);
+        if (hi) sh.hash_lo = std::min(sh.hash_lo, lo), sh.hash_hi = std::max(sh.hash_hi, hi);
+        return true;
+      });
+      if (!sh.hash_hi) sh.hash_lo = 0;
+      rcs[d] = bv_evf_launch(c, x, f, sh, &calls[d]);
+      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.z - sh.a, calls[d].d_bits);
+    });
+  for (auto &t : th) t.join();
+  for (int d = 0; d < D; d++)
+    if (rcs[d] != BV_OK) return gfail(g, rcs[d], "device " + std::to_string(g->devices[d]) + ": " + g->ctx[d]->err);
+
+  std::vector<uint64_t> gathered;
+  const int rc = gather_and_finish(g, words, gathered, [&](int d, bv_ctx *c) {
+    if (bounds[d + 1] == bounds[d]) return (int)BV_OK;  // an empty shard launched nothing
+    bv_result sr = shard_res(d);
+    bv_event_itx_out so = shard_out(d);
+    return bv_evf_finish(c, &sr, out ? &so : nullptr, &calls[d], false);
+  });
+  if (rc != BV_OK) return rc;
+  if (res->accept_bits && bv_merge_shard_bits(gathered.data(), words, D, bounds.data(), res->accept_bits) != BV_OK)
+    return gfail(g, BV_E_ARGS, "merge shard bits");
+  return BV_OK;
+}
+
+extern "C" int bv_group_verify_events_itx(bv_group *g, const bv_event_itx_batch *x, bv_result *res,
+                                          bv_event_itx_out *out) {
+  if (!g || !x || !res) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const int rc = group_verify_events_fields(g, x, nullptr, res, out);
+  if (rc != BV_OK) drain_all(g, rc);
+  return rc;
+}
+
+extern "C" int bv_group_verify_events_fields(bv_group *g, const bv_event_fields_batch *f, bv_result *res,
+                                             bv_event_itx_out *out) {
+  if (!g || !f || !res) return BV_E_ARGS;
+  std::lock_guard<std::mutex> lk(g->mu);
+  const int rc = group_verify_events_fields(g, &f->ev, f, res, out);
   if (rc != BV_OK) drain_all(g, rc);
   return rc;
 }
@@ -546,7 +680,7 @@ static int group_verify_blocks(bv_group *g, const bv_block_batch *k, bv_result *
       const bv_blk_shard sh{bb[d], bb[d + 1], ib[d], ib[d + 1]};
       const bv_result sr = shard_res(d);
       rcs[d] = bv_blocks_launch(c, k, sh, &sr, shard_cnt(d), &calls[d], text);
-      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.b1 > sh.b0 ? sh.i1 - sh.i0 : 0);
+      if (rcs[d] == BV_OK) rcs[d] = stage_shard_bits(g, d, words, sh.b1 > sh.b0 ? sh.i1 - sh.i0 : 0, c->S().bits.p);
     });
   for (auto &t : th) t.join();
   for (int d = 0; d < D; d++)

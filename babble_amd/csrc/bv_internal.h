@@ -32,6 +32,8 @@
 
 struct EvjBases;
 struct BlkBases;
+struct ItxBases;
+struct BsigBases;
 namespace bvk {
 hipError_t sha256(hipStream_t, uint64_t, const uint8_t *, const uint64_t *, uint32_t *, uint64_t max_len = ~0ull);
 hipError_t put_digests(hipStream_t, uint64_t, const uint64_t *, const uint32_t *, uint32_t *);
@@ -67,6 +69,17 @@ hipError_t ev_compose(hipStream_t st, uint64_t n_ev, const uint64_t *itx_start, 
 // ev_body_hash_itx with the BlockSignatures member built from fields too (fields_kernels.hip, bsigjson.h)
 hipError_t ev_body_hash_fields(hipStream_t st, const bv_event_fields_batch &f, uint64_t e0, uint64_t e1,
                                uint32_t *dig);
+// the three body-hash kernels and the fold over a shard's slices (EvjBases, ItxBases, BsigBases): [e0, e1) are
+// the whole batch's event indices; dig, the ITX index and every array of the fold but itx_start are the shard's
+hipError_t itx_body_hash_rb(hipStream_t st, const bv_event_itx_batch &x, uint64_t n_itx, uint64_t n_ev,
+                            const ItxBases &ib, uint32_t *dig);
+hipError_t ev_body_hash_itx_rb(hipStream_t st, const bv_event_itx_batch &x, uint64_t e0, uint64_t e1,
+                               const EvjBases &bs, const ItxBases &ib, uint32_t *dig);
+hipError_t ev_body_hash_fields_rb(hipStream_t st, const bv_event_fields_batch &f, uint64_t e0, uint64_t e1,
+                                  const EvjBases &bs, const ItxBases &ib, const BsigBases &sb, uint32_t *dig);
+hipError_t ev_compose_rb(hipStream_t st, uint64_t n_ev, const uint64_t *itx_start, uint64_t itx_base,
+                         const uint8_t *item_status, const uint8_t *force_panic, uint8_t *ev_status,
+                         uint32_t *decided_by, uint64_t *bits, uint8_t *itx_status);
 hipError_t iota(hipStream_t, uint64_t, uint32_t *);
 hipError_t sig_decode(hipStream_t, uint64_t n, const uint64_t *off, const uint8_t *text, uint8_t *r_be, uint8_t *s_be,
                       uint8_t *pre);
@@ -475,4 +488,34 @@ bool bv_blocks_small(bv_ctx *ctx, const bv_block_batch *blocks, bool text);
 int bv_blocks_launch(bv_ctx *ctx, const bv_block_batch *blocks, const bv_blk_shard &sh, const bv_result *res,
                      uint32_t *valid_count, bv_blk_call *call, bool text);
 int bv_blocks_finish(bv_ctx *ctx, bv_result *res, uint32_t *valid_count, bv_blk_call *call, bool bits_out);
+// bv_verify_events_itx / bv_verify_events_fields' bulk pipeline over one event
+// range of a batch (bv_event_itx.cpp; `f`: the fields batch, x == &f->ev, or
+// null for the ITX entry): events [a, z), the ITXs, block signatures and
+// transactions they own and the parent hashes [hash_lo, hash_hi).
+// bv_evf_validate checks the WHOLE batch once (*route: EVF_RUN, or which
+// fall-back entry takes the batch: bv_evf_no_itx / bv_evf_no_bsig, called
+// without a ctx locked); bv_evf_try_small is the single-context entries'
+// routing decision for the whole batch (*taken: it ran on the one-launch small
+// path and the results are written); bv_evf_launch builds the range's keys and
+// signature text on the ctx's pool and enqueues its staging, hashing, verify
+// and fold; bv_evf_finish collects after bv_mark_done (`res`, `out`: the
+// range's result pointers).  An empty range launches nothing (skip its finish).
+enum { EVF_RUN, EVF_NO_ITX, EVF_NO_BSIG };
+struct bv_evf_call {
+  bv_host_call host;
+  uint64_t n = 0, m = 0;         // the range's events and ITXs
+  size_t p_ist = 0, p_dby = 0;   // itx_status and decided_by in host.pout
+  const void *d_bits = nullptr;  // the range's accept words on the device (k_ev_compose's)
+};
+int bv_evf_validate(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, int *route);
+int bv_evf_try_small(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, bv_result *res,
+                     bv_event_itx_out *out, bool *taken);
+int bv_evf_launch(bv_ctx *ctx, const bv_event_itx_batch *x, const bv_event_fields_batch *f, const bv_ev_shard &sh,
+                  bv_evf_call *call);
+int bv_evf_finish(bv_ctx *ctx, bv_result *res, bv_event_itx_out *out, bv_evf_call *call, bool bits_out);
+int bv_evf_no_itx(const bv_event_itx_batch *x, bv_result *res, bv_event_itx_out *out,
+                  const std::function<int(const bv_event_batch *, bv_result *)> &verify_events);
+int bv_evf_no_bsig(const bv_event_fields_batch *f, bv_result *res, bv_event_itx_out *out,
+                   const std::function<int(const bv_event_itx_batch *, bv_result *, bv_event_itx_out *)> &verify_itx,
+                   const std::function<int(const bv_event_batch *, bv_result *)> &verify_events);
 void bv_read_timing(bv_ctx *ctx);

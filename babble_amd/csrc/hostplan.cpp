@@ -9,6 +9,9 @@
 //   bv_merge_shard_bits  the accept bitmask from the all-gathered shard words;
 //   bv_plan_event_shards the plan of bv_group_verify_events: 64-aligned event
 //                        shards and each shard's range of parent hashes;
+//   bv_plan_event_fields_shards  the plan of bv_group_verify_events_itx /
+//                        _fields: that plan, and the ITXs and block
+//                        signatures each shard's events own;
 //   bv_plan_block_shards the plan of bv_group_verify_blocks: bv_plan_group's
 //                        item shards and message partition over the blocks.
 //
@@ -82,6 +85,24 @@ extern "C" int bv_plan_event_shards(const bv_event_batch *b, int n_shards, uint6
   for (int d = 0; d < n_shards; d++)
     if (!event_hash_range(b, event_bounds[d], event_bounds[d + 1], &hash_lo[d], &hash_hi[d])) return BV_E_ARGS;
   return dag ? 1 : 0;
+}
+
+// The plan of bv_group_verify_events_itx / _fields: bv_plan_event_shards' event
+// bounds and hash ranges (shards balanced by events, not items: ITXs are
+// rare), and what else a shard owns, read off the batch's own start arrays at
+// those bounds.
+extern "C" int bv_plan_event_fields_shards(const bv_event_fields_batch *f, int n_shards, uint64_t *event_bounds,
+                                           uint64_t *itx_bounds, uint64_t *bsig_bounds, uint64_t *hash_lo,
+                                           uint64_t *hash_hi) {
+  if (!f || !itx_bounds || !bsig_bounds) return BV_E_ARGS;
+  const int rc = bv_plan_event_shards(&f->ev.events, n_shards, event_bounds, hash_lo, hash_hi);
+  if (rc < 0) return rc;
+  if (f->ev.events.n_events && !f->bsig_start) return BV_E_ARGS;
+  for (int d = 0; d <= n_shards; d++) {
+    itx_bounds[d] = f->ev.itx_start ? f->ev.itx_start[event_bounds[d]] : 0;
+    bsig_bounds[d] = f->bsig_start ? f->bsig_start[event_bounds[d]] : 0;
+  }
+  return rc;
 }
 
 void plan_event_bounds(uint64_t n, int D, bool dag, uint64_t *bounds) {

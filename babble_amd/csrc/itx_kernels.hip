@@ -50,6 +50,41 @@ __global__ void __launch_bounds__(EVI_NT) k_ev_body_hash_itx(bv_event_itx_batch 
   dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
 }
 
+// The two kernels above over a shard's slices (bv_group_verify_events_itx;
+// evjson.h EvjBases, itxjson.h ItxBases): the arrays of `x` start at the
+// shard's first event / transaction / ITX / byte and the values in them are
+// the whole batch's.  The same launch shapes and LDS row sinks.  i is the
+// shard's ITX index and n_ev the shard's event count; [e0, e1) are the whole
+// batch's event indices and dig is the shard's (event e is row e - bs.ev).
+__global__ void __launch_bounds__(ITX_NT) k_itx_body_hash_rb(bv_event_itx_batch x, uint64_t n_itx, uint64_t n_ev,
+                                                             ItxBases ib, uint32_t *__restrict__ dig) {
+  __shared__ uint32_t rows[ITX_NT * ITX_ROW];
+  const uint64_t i = (uint64_t)blockIdx.x * ITX_NT + threadIdx.x;
+  if (i >= n_itx) return;  // no barriers below
+  EvjSha o = evj_sha_begin(rows + threadIdx.x * ITX_ROW);
+  itx_body_emit(x, i, o, ib);
+  uint32_t be[8];
+  evj_sha_finish(o, be);
+  uint4 *dst = (uint4 *)(dig + 8 * (n_ev + i));
+  dst[0] = make_uint4(be[0], be[1], be[2], be[3]);
+  dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
+}
+
+__global__ void __launch_bounds__(EVI_NT) k_ev_body_hash_itx_rb(bv_event_itx_batch x, uint64_t e0, uint64_t e1,
+                                                                EvjBases bs, ItxBases ib,
+                                                                uint32_t *__restrict__ dig) {
+  __shared__ uint32_t rows[EVI_NT * EVI_ROW];
+  const uint64_t e = e0 + (uint64_t)blockIdx.x * EVI_NT + threadIdx.x;
+  if (e >= e1) return;  // no barriers below
+  EvjSha o = evj_sha_begin(rows + threadIdx.x * EVI_ROW);
+  evj_emit(x, e, o, bs, ib);
+  uint32_t be[8];
+  evj_sha_finish(o, be);
+  uint4 *dst = (uint4 *)(dig + 8 * (e - bs.ev));
+  dst[0] = make_uint4(be[0], be[1], be[2], be[3]);
+  dst[1] = make_uint4(be[4], be[5], be[6], be[7]);
+}
+
 // Event.Verify's fold (event.go:219-247), one lane per event: item e is the
 // event signature, item n_ev + i ITX i; an ITX with force_panic set is
 // BV_REF_PANIC whatever its item says (PubKeyHex shorter than 2 bytes: Go
@@ -84,6 +119,26 @@ __global__ void __launch_bounds__(256) k_ev_compose(uint64_t n_ev, const uint64_
   if ((threadIdx.x & 63) == 0 && e < n_ev) bits[e >> 6] = word;
 }
 
+// k_ev_compose over a shard: itx_start holds the whole batch's values from the
+// shard's first event on, while item_status, force_panic, itx_status and the
+// outputs are the shard's own (its first ITX is the batch's ITX itx_base).
+// The fold is ev_fold (itxjson.h), which the host emulator runs too;
+// k_ev_compose keeps its own copy so that its code stays what it was,
+// instruction for instruction.
+__global__ void __launch_bounds__(256) k_ev_compose_rb(uint64_t n_ev, const uint64_t *__restrict__ itx_start,
+                                                       uint64_t itx_base, const uint8_t *__restrict__ item_status,
+                                                       const uint8_t *__restrict__ force_panic,
+                                                       uint8_t *__restrict__ ev_status,
+                                                       uint32_t *__restrict__ decided_by, uint64_t *__restrict__ bits,
+                                                       uint8_t *__restrict__ itx_status) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool acc = false;
+  if (e < n_ev)
+    acc = ev_fold(n_ev, e, itx_start, itx_base, item_status, force_panic, ev_status, decided_by, itx_status);
+  const uint64_t word = __ballot(acc);
+  if ((threadIdx.x & 63) == 0 && e < n_ev) bits[e >> 6] = word;
+}
+
 namespace bvk {
 static inline dim3 grid1(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
 
@@ -96,6 +151,29 @@ hipError_t itx_body_hash(hipStream_t st, const bv_event_itx_batch &x, uint64_t n
 hipError_t ev_body_hash_itx(hipStream_t st, const bv_event_itx_batch &x, uint64_t e0, uint64_t e1, uint32_t *dig) {
   if (e1 <= e0) return hipSuccess;
   hipLaunchKernelGGL(k_ev_body_hash_itx, grid1(e1 - e0, EVI_NT), dim3(EVI_NT), 0, st, x, e0, e1, dig);
+  return hipGetLastError();
+}
+
+hipError_t itx_body_hash_rb(hipStream_t st, const bv_event_itx_batch &x, uint64_t n_itx, uint64_t n_ev,
+                            const ItxBases &ib, uint32_t *dig) {
+  if (n_itx == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_itx_body_hash_rb, grid1(n_itx, ITX_NT), dim3(ITX_NT), 0, st, x, n_itx, n_ev, ib, dig);
+  return hipGetLastError();
+}
+
+hipError_t ev_body_hash_itx_rb(hipStream_t st, const bv_event_itx_batch &x, uint64_t e0, uint64_t e1,
+                               const EvjBases &bs, const ItxBases &ib, uint32_t *dig) {
+  if (e1 <= e0) return hipSuccess;
+  hipLaunchKernelGGL(k_ev_body_hash_itx_rb, grid1(e1 - e0, EVI_NT), dim3(EVI_NT), 0, st, x, e0, e1, bs, ib, dig);
+  return hipGetLastError();
+}
+
+hipError_t ev_compose_rb(hipStream_t st, uint64_t n_ev, const uint64_t *itx_start, uint64_t itx_base,
+                         const uint8_t *item_status, const uint8_t *force_panic, uint8_t *ev_status,
+                         uint32_t *decided_by, uint64_t *bits, uint8_t *itx_status) {
+  if (n_ev == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ev_compose_rb, grid1(n_ev, 256), dim3(256), 0, st, n_ev, itx_start, itx_base, item_status,
+                     force_panic, ev_status, decided_by, bits, itx_status);
   return hipGetLastError();
 }
 

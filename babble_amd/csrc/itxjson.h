@@ -131,24 +131,40 @@ DEV uint64_t gojson_string_len(const uint8_t *s, uint64_t n) {
 #define ITX_PUBKEYHEX 1
 #define ITX_MONIKER 2
 #define ITX_SIGNATURE 3
-DEV const uint8_t *itx_str_ptr(const bv_event_itx_batch &x, uint64_t i, int k) {
-  return x.itx_str + x.itx_str_off[4 * i + k];
+// Bases of a shard (bv_group_verify_events_itx / _fields), as EvjBases: the ITX
+// arrays of `x` are the slices one event range of a larger batch needs, and
+// the values in itx_start and itx_str_off are still the whole batch's.
+//   itx  itx_start[a]: itx_type and itx_str_off start at that ITX (an ITX
+//        index passed to the functions below is already the slice's, i - itx)
+//   str  itx_str_off[4 * itx]: itx_str starts at that byte
+// ItxNoBases (all zero, compile-time) is the whole batch: the subtractions
+// fold away and the emitters compile as they did without them.
+struct ItxBases {
+  uint64_t itx, str;
+};
+struct ItxNoBases {
+  static constexpr uint64_t itx = 0, str = 0;
+};
+
+template <class B = ItxNoBases>
+DEV const uint8_t *itx_str_ptr(const bv_event_itx_batch &x, uint64_t i, int k, const B &bs = B{}) {
+  return x.itx_str + (x.itx_str_off[4 * i + k] - bs.str);
 }
 DEV uint64_t itx_str_len(const bv_event_itx_batch &x, uint64_t i, int k) {
   return x.itx_str_off[4 * i + k + 1] - x.itx_str_off[4 * i + k];
 }
 
 // {"Type":T,"Peer":{...}} of ITX i: the body without Marshal's newline
-template <class O>
-DEV void itx_body_json(const bv_event_itx_batch &x, uint64_t i, O &o) {
+template <class O, class B = ItxNoBases>
+DEV void itx_body_json(const bv_event_itx_batch &x, uint64_t i, O &o, const B &bs = B{}) {
   evj_lit(o, ITX_L0);
   evj_dec(o, (int64_t)x.itx_type[i]);
   evj_lit(o, ITX_L1);
-  gojson_string(o, itx_str_ptr(x, i, ITX_NETADDR), itx_str_len(x, i, ITX_NETADDR));
+  gojson_string(o, itx_str_ptr(x, i, ITX_NETADDR, bs), itx_str_len(x, i, ITX_NETADDR));
   evj_lit(o, ITX_L2);
-  gojson_string(o, itx_str_ptr(x, i, ITX_PUBKEYHEX), itx_str_len(x, i, ITX_PUBKEYHEX));
+  gojson_string(o, itx_str_ptr(x, i, ITX_PUBKEYHEX, bs), itx_str_len(x, i, ITX_PUBKEYHEX));
   evj_lit(o, ITX_L3);
-  gojson_string(o, itx_str_ptr(x, i, ITX_MONIKER), itx_str_len(x, i, ITX_MONIKER));
+  gojson_string(o, itx_str_ptr(x, i, ITX_MONIKER, bs), itx_str_len(x, i, ITX_MONIKER));
   evj_lit(o, ITX_L4);
 }
 
@@ -160,20 +176,20 @@ DEV uint64_t itx_body_json_len(const bv_event_itx_batch &x, uint64_t i) {
 }
 
 // InternalTransactionBody.Marshal() of ITX i (what its Signature is over)
-template <class O>
-DEV void itx_body_emit(const bv_event_itx_batch &x, uint64_t i, O &o) {
-  itx_body_json(x, i, o);
+template <class O, class B = ItxNoBases>
+DEV void itx_body_emit(const bv_event_itx_batch &x, uint64_t i, O &o, const B &bs = B{}) {
+  itx_body_json(x, i, o, bs);
   o.put('\n');
 }
 DEV uint64_t itx_body_len(const bv_event_itx_batch &x, uint64_t i) { return itx_body_json_len(x, i) + 1; }
 
 // One element of EventBody.InternalTransactions
-template <class O>
-DEV void itx_elem_emit(const bv_event_itx_batch &x, uint64_t i, O &o) {
+template <class O, class B = ItxNoBases>
+DEV void itx_elem_emit(const bv_event_itx_batch &x, uint64_t i, O &o, const B &bs = B{}) {
   evj_lit(o, ITX_E0);
-  itx_body_json(x, i, o);
+  itx_body_json(x, i, o, bs);
   evj_lit(o, ITX_E1);
-  gojson_string(o, itx_str_ptr(x, i, ITX_SIGNATURE), itx_str_len(x, i, ITX_SIGNATURE));
+  gojson_string(o, itx_str_ptr(x, i, ITX_SIGNATURE, bs), itx_str_len(x, i, ITX_SIGNATURE));
   o.put('}');
 }
 DEV uint64_t itx_elem_len(const bv_event_itx_batch &x, uint64_t i) {
@@ -195,16 +211,16 @@ DEV uint64_t itx_list_len(const bv_event_itx_batch &x, uint64_t e) {
   return n;
 }
 
-template <class O>
-DEV void itx_list_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
+template <class O, class B = ItxNoBases>
+DEV void itx_list_emit(const bv_event_itx_batch &x, uint64_t e, O &o, const B &bs = B{}) {
   if (itx_list_is_nil(x, e)) {
     evj_lit(o, "null");
   } else {
-    const uint64_t i0 = x.itx_start[e], i1 = x.itx_start[e + 1];
+    const uint64_t i0 = x.itx_start[e] - bs.itx, i1 = x.itx_start[e + 1] - bs.itx;
     o.put('[');
     for (uint64_t i = i0; i < i1; i++) {
       if (i > i0) o.put(',');
-      itx_elem_emit(x, i, o);
+      itx_elem_emit(x, i, o, bs);
     }
     o.put(']');
   }
@@ -214,14 +230,43 @@ DEV uint64_t evj_len(const bv_event_itx_batch &x, uint64_t e, uint32_t ppos[2]) 
   return evj_len_rest(x.events, e, evj_len_txs(x.events, e) + itx_list_len(x, e), ppos);
 }
 
-template <class O>
-DEV void evj_emit(const bv_event_itx_batch &x, uint64_t e, O &o) {
-  evj_emit_txs(x.events, e, o);
-  itx_list_emit(x, e, o);
-  evj_emit_rest(x.events, e, o);
+// (bs, ib: a shard's bases; `e` is then the whole batch's index, as evj_emit's)
+template <class O, class B = EvjNoBases, class IB = ItxNoBases>
+DEV void evj_emit(const bv_event_itx_batch &x, uint64_t e, O &o, const B &bs = B{}, const IB &ib = IB{}) {
+  e -= bs.ev;
+  evj_emit_txs(x.events, e, o, bs);
+  itx_list_emit(x, e, o, ib);
+  evj_emit_rest(x.events, e, o, bs);
 }
 
 DEV void evj_write(const bv_event_itx_batch &x, uint64_t e, uint8_t *o) {
   EvjMem m{o};
   evj_emit(x, e, m);
+}
+
+// Event.Verify's fold for event e (event.go:219-247) over the item statuses:
+// item e is the event signature, item n_ev + i ITX i; an ITX with force_panic
+// set is BV_REF_PANIC whatever its item says.  The first ITX of the event that
+// is not ACCEPT decides it, else the event signature does.  Writes the event's
+// status and decided_by and its ITXs' own statuses; returns status ==
+// BV_ACCEPT.  itx_base: itx_start holds a larger batch's values while every
+// other array starts at the shard's first event / ITX (0: the whole batch).
+DEV bool ev_fold(uint64_t n_ev, uint64_t e, const uint64_t *__restrict__ itx_start, uint64_t itx_base,
+                 const uint8_t *__restrict__ item_status, const uint8_t *__restrict__ force_panic,
+                 uint8_t *__restrict__ ev_status, uint32_t *__restrict__ decided_by,
+                 uint8_t *__restrict__ itx_status) {
+  uint8_t st = item_status[e];
+  uint32_t by = BV_EV_SELF;
+  const uint64_t i0 = itx_start[e] - itx_base, i1 = itx_start[e + 1] - itx_base;
+  for (uint64_t i = i0; i < i1; i++) {
+    const uint8_t c = force_panic[i] ? (uint8_t)BV_REF_PANIC : item_status[n_ev + i];
+    itx_status[i] = c;
+    if (by == BV_EV_SELF && c != BV_ACCEPT) {
+      by = (uint32_t)(i - i0);
+      st = c == BV_REJECT ? (uint8_t)BV_EV_ITX_INVALID : c;
+    }
+  }
+  ev_status[e] = st;
+  decided_by[e] = by;
+  return st == BV_ACCEPT;
 }

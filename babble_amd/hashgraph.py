@@ -329,7 +329,7 @@ def verify_itxs(itxs: Sequence[InternalTransaction], verifier=None, text: bool =
     return out
 
 
-def verify_events(events: Sequence[Event], verifier=None, fields: bool = False) -> List[Outcome]:
+def verify_events(events: Sequence[Event], verifier=None, fields: bool = False, group=None) -> List[Outcome]:
     """Event.Verify for every event in one device batch.  Each event's digest
     is stored in its `_hash` (so Hex() does not hash again, cf. the second
     JSON+SHA-256 in initEventCoordinates, hashgraph.go:474-479).
@@ -337,9 +337,13 @@ def verify_events(events: Sequence[Event], verifier=None, fields: bool = False) 
     InternalTransactions go to the library as fields and ONE
     bv_verify_events_itx call builds, hashes, verifies and folds them; when
     an event carries BlockSignatures they go as fields too
-    (bv_verify_events_fields)."""
+    (bv_verify_events_fields).
+    group (with fields=True): a verifier.Group; the one call then goes to it
+    (bv_group_verify_events_itx / _fields: sharded by event index)."""
+    if group is not None and not fields:
+        raise ValueError("group= needs fields=True")
     if fields:
-        return _verify_events_fields(events, verifier)
+        return _verify_events_fields(events, group or verifier)
     bb = BatchBuilder()
     plan = []  # per event: ([itx item or None], event item, msg index)
     for ev in events:

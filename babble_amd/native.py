@@ -43,6 +43,7 @@ EXPORTS = (
     "bv_verify_events_itx", "bv_itx_body_lens", "bv_itx_bodies", "bv_event_itx_body_lens", "bv_event_itx_bodies",
     "bv_verify_events_fields", "bv_event_fields_body_lens", "bv_event_fields_bodies",
     "bv_group_verify_blocks", "bv_plan_block_shards",
+    "bv_group_verify_events_itx", "bv_group_verify_events_fields", "bv_plan_event_fields_shards",
 )
 
 
@@ -219,6 +220,12 @@ def lib() -> ctypes.CDLL:
     L.bv_group_verify_blocks.restype = ctypes.c_int
     L.bv_plan_block_shards.argtypes = [ctypes.POINTER(BvBlockBatch), ctypes.c_int, P, P]
     L.bv_plan_block_shards.restype = ctypes.c_int
+    L.bv_group_verify_events_itx.argtypes = [P, P, ctypes.POINTER(BvResult), P]
+    L.bv_group_verify_events_itx.restype = ctypes.c_int
+    L.bv_group_verify_events_fields.argtypes = [P, P, ctypes.POINTER(BvResult), P]
+    L.bv_group_verify_events_fields.restype = ctypes.c_int
+    L.bv_plan_event_fields_shards.argtypes = [P, ctypes.c_int, P, P, P, P, P]
+    L.bv_plan_event_fields_shards.restype = ctypes.c_int
     L.bv_arena_create.argtypes = [ctypes.POINTER(P)]
     L.bv_arena_create.restype = ctypes.c_int
     L.bv_arena_destroy.argtypes = [P]

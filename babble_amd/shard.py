@@ -92,6 +92,19 @@ def plan_event_shards(parent_kind, parent_ref, n_shards: int):
     return dag, bounds, lo, hi
 
 
+def plan_event_fields_shards(parent_kind, parent_ref, itx_start, bsig_start, n_shards: int):
+    """bv_plan_event_fields_shards (csrc/hostplan.cpp) restated: (dag, bounds,
+    itx_bounds, bsig_bounds, hash_lo, hash_hi).  The event bounds and hash
+    ranges are `plan_event_shards`' (shards balanced by events: ITXs are
+    rare); shard d owns the ITXs and block signatures its events own, read off
+    the batch's start arrays at the bounds (itx_start None: no ITX fields, all
+    0)."""
+    dag, bounds, lo, hi = plan_event_shards(parent_kind, parent_ref, n_shards)
+    ib = [0 if itx_start is None else int(itx_start[b]) for b in bounds]
+    bb = [0 if bsig_start is None else int(bsig_start[b]) for b in bounds]
+    return dag, bounds, ib, bb, lo, hi
+
+
 def plan_block_shards(item_block, n_blocks: int, n_shards: int):
     """bv_plan_block_shards (csrc/hostplan.cpp) restated: (unsorted,
     block_bounds, item_bounds).  Items sorted by block follow `plan_group`

@@ -50,6 +50,31 @@ def _p(a: np.ndarray) -> int:
     return a.ctypes.data if a is not None and a.size else 0
 
 
+def _event_itx_result(n: int, m: int) -> EventItxVerifyResult:
+    """Result arrays for n events and m ITXs (at least one element each)."""
+    return EventItxVerifyResult(np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8),
+                                np.zeros(max((n + 63) // 64, 1), np.uint64), np.zeros((max(m, 1), 32), np.uint8),
+                                np.zeros(max(m, 1), np.uint8), np.zeros(max(n, 1), np.uint32))
+
+
+def _event_itx_call(fn, handle, xb, res: EventItxVerifyResult) -> int:
+    """One of the four one-call event entries (single context or group, ITX or
+    fields batch) into caller-owned result arrays, any of them None."""
+    from .events import BvEventItxOut
+
+    keep: list = []
+    cb = xb.c_struct(keep)
+    r = native.BvResult(_p(res.msg_hash), _p(res.status), _p(res.accept_bits))
+    out = BvEventItxOut(_p(getattr(res, "itx_hash", None)), _p(getattr(res, "itx_status", None)),
+                        _p(getattr(res, "decided_by", None)))
+    return fn(handle, ctypes.byref(cb), ctypes.byref(r), ctypes.byref(out))
+
+
+def _event_itx_trim(res: EventItxVerifyResult, n: int, m: int) -> EventItxVerifyResult:
+    return EventItxVerifyResult(res.msg_hash[:n], res.status[:n], res.accept_bits[: (n + 63) // 64],
+                                res.itx_hash[:m], res.itx_status[:m], res.decided_by[:n])
+
+
 class DeviceBatch:
     """Device-resident copy of a PackedBatch plus its result buffers."""
 
@@ -313,6 +338,20 @@ class Verifier:
                                                     ctypes.byref(out)))
         return EventItxVerifyResult(h[:n], st[:n], bits[: (n + 63) // 64], ih[:m], ist[:m], by[:n])
 
+    def verify_events_itx_into(self, xb, res: "EventItxVerifyResult") -> "EventItxVerifyResult":
+        """bv_verify_events_itx into caller-owned result arrays, any of them
+        None (the inputs of a batch built by PinnedArena.event_itx_batch are
+        reached by DMA)."""
+        self._check(_event_itx_call(self._L.bv_verify_events_itx, self._ctx, xb, res))
+        return res
+
+    def verify_events_fields_into(self, fb, res: "EventItxVerifyResult") -> "EventItxVerifyResult":
+        """bv_verify_events_fields into caller-owned result arrays, any of them
+        None (the inputs of a batch built by PinnedArena.event_fields_batch
+        are reached by DMA)."""
+        self._check(_event_itx_call(self._L.bv_verify_events_fields, self._ctx, fb, res))
+        return res
+
     def peer_set_hash(self, pubkeys: Sequence[bytes]) -> bytes:
         """bv_peer_set_hash: PeerSet.Hash over the peers' key bytes (b"" for
         an empty set, as Go's []byte{})."""
@@ -539,6 +578,36 @@ class Group:
         self._check(self._L.bv_group_verify_blocks(self._g, ctypes.byref(cb), ctypes.byref(r), _p(vc) or None))
         return res
 
+    def verify_events_itx(self, xb) -> "EventItxVerifyResult":
+        """bv_group_verify_events_itx over an events.PackedEventItxBatch: the
+        whole of Event.Verify in one call, as Verifier.verify_events_itx; a
+        bulk batch is sharded by event index (a shard owns its events' ITXs),
+        a batch with in-batch parents or a small one runs on slot 0."""
+        n, m = xb.n_events, xb.n_itx
+        return _event_itx_trim(self.verify_events_itx_into(xb, _event_itx_result(n, m)), n, m)
+
+    def verify_events_itx_into(self, xb, res: "EventItxVerifyResult") -> "EventItxVerifyResult":
+        """bv_group_verify_events_itx into caller-owned result arrays, any of
+        them None (the inputs of a batch built by PinnedArena.event_itx_batch
+        are DMA'd to every device from where they lie)."""
+        self._check(_event_itx_call(self._L.bv_group_verify_events_itx, self._g, xb, res))
+        return res
+
+    def verify_events_fields(self, fb) -> "EventItxVerifyResult":
+        """bv_group_verify_events_fields over an events.PackedEventFieldsBatch:
+        as verify_events_itx, with the BlockSignatures built from fields too
+        (a shard owns its events' block signatures as well)."""
+        n, m = fb.n_events, fb.n_itx
+        return _event_itx_trim(self.verify_events_fields_into(fb, _event_itx_result(n, m)), n, m)
+
+    def verify_events_fields_into(self, fb, res: "EventItxVerifyResult") -> "EventItxVerifyResult":
+        """bv_group_verify_events_fields into caller-owned result arrays, any
+        of them None (the inputs of a batch built by
+        PinnedArena.event_fields_batch are DMA'd to every device from where
+        they lie)."""
+        self._check(_event_itx_call(self._L.bv_group_verify_events_fields, self._g, fb, res))
+        return res
+
     def register_keys(self, pubkeys: Sequence[bytes]) -> None:
         """bv_group_kc_register: the validator set for every slot's key cache
         (a group created with F_KEY_CACHE)."""
@@ -585,6 +654,22 @@ def plan_event_shards(eb, n_shards: int):
     return bool(rc), bounds, lo[:n_shards], hi[:n_shards]
 
 
+def plan_event_fields_shards(fb, n_shards: int):
+    """bv_plan_event_fields_shards: (dag, event_bounds, itx_bounds,
+    bsig_bounds, hash_lo, hash_hi) — the plan bv_group_verify_events_itx /
+    _fields follow for an events.PackedEventFieldsBatch (host only)."""
+    keep: list = []
+    cb = fb.c_struct(keep)
+    eb, ib, bb = (np.zeros(n_shards + 1, np.uint64) for _ in range(3))
+    lo = np.zeros(max(n_shards, 1), np.uint64)
+    hi = np.zeros(max(n_shards, 1), np.uint64)
+    rc = native.lib().bv_plan_event_fields_shards(ctypes.byref(cb), n_shards, eb.ctypes.data, ib.ctypes.data,
+                                                  bb.ctypes.data, lo.ctypes.data, hi.ctypes.data)
+    if rc < 0:
+        raise native.BvError(rc, "bv_plan_event_fields_shards")
+    return bool(rc), eb, ib, bb, lo[:n_shards], hi[:n_shards]
+
+
 def plan_block_shards(pb, n_shards: int):
     """bv_plan_block_shards: (unsorted, block_bounds, item_bounds) — the plan
     bv_group_verify_blocks follows for a batch.PackedBlockBatch (host only)."""
@@ -615,8 +700,11 @@ class PinnedArena:
     DMA'd by bv_verify_batch without the staging copy (what the cgo shim does
     instead of C.CBytes).  Freed with close()."""
 
-    def __init__(self):
-        self._L = native.lib()
+    def __init__(self, lib=None):
+        """lib: another loaded build of the library whose bv_host_alloc /
+        bv_host_free own the blocks (development tools that run two builds
+        side by side); by default this package's."""
+        self._L = lib if lib is not None else native.lib()
         self._blocks = []
 
     def array(self, shape, dtype) -> np.ndarray:

@@ -376,7 +376,7 @@ int bv_verify_events(bv_ctx *ctx, const bv_event_batch *events, bv_result *resul
  * itx_type NULL while n_itx > 0; n_events + n_itx > 2^32.  n_itx == 0 is
  * valid and returns exactly what bv_verify_events returns for the same events
  * with nil or "[]" fragments.
- * Single device only: bv_group_verify_events takes no ITX fields. */
+ * Over several devices: bv_group_verify_events_itx below. */
 #define BV_EV_ITX_INVALID 4 /* (false, "invalid signature on internal transaction") */
 #define BV_EV_SELF 0xFFFFFFFFu
 typedef struct {
@@ -436,7 +436,7 @@ int bv_event_itx_bodies(const bv_event_itx_batch *batch, const uint64_t *off, ui
  * with bytes named and bsig_val_bytes NULL; n_bsig > 2^32.  n_bsig == 0 is
  * valid and returns exactly what bv_verify_events_itx (for a NULL itx_start:
  * bv_verify_events) returns for the same events with nil or "[]" fragments.
- * Single device only: bv_group_verify_events keeps the fragments. */
+ * Over several devices: bv_group_verify_events_fields below. */
 #define BV_BSIG_VAL_CREATOR 0 /* Validator = the event's creator key bytes (WireEvent.BlockSignatures) */
 #define BV_BSIG_VAL_BYTES   1 /* Validator = bsig_val_bytes[bsig_val_off[j] .. bsig_val_off[j+1]) (any length, 0 -> "") */
 #define BV_BSIG_VAL_NIL     2 /* Validator is a nil []byte -> null */
@@ -548,6 +548,59 @@ int bv_group_kc_register(bv_group *g, uint32_t n_keys, const uint8_t *key_bytes,
  * n_parent_hashes are read. */
 int bv_plan_event_shards(const bv_event_batch *events, int n_shards, uint64_t *event_bounds, uint64_t *hash_lo,
                          uint64_t *hash_hi);
+
+/* bv_verify_events_itx / bv_verify_events_fields over the group: the whole of
+ * Event.Verify in one call, sharded by event index.  The result contract, the
+ * validation rules with their BV_E_ARGS cases and texts (checked once over the
+ * whole batch; the text in bv_group_last_error), the pinned-memory rule for
+ * the inputs and the semantics of `out` are exactly those of the
+ * single-context entries; msg_hash, status, accept_bits, out and every member
+ * of out may be NULL.  The fall-back equalities hold through the group too:
+ * n_itx == 0 (bv_group_verify_events_itx) returns what bv_group_verify_events
+ * returns for the same events with nil or "[]" fragments, n_bsig == 0
+ * (bv_group_verify_events_fields) what bv_group_verify_events_itx (for a NULL
+ * itx_start: bv_group_verify_events) returns.
+ * A batch without BV_PARENT_EVENT parents that the single-context entry would
+ * send down its bulk pipeline is cut at the bounds of bv_plan_event_shards
+ * (whole 64-event words per slot, trailing shards possibly empty): the shards
+ * are balanced by EVENTS, not by items, because ITXs are rare.  Shard [a, z)
+ * owns the ITXs [itx_start[a], itx_start[z]), the block signatures
+ * [bsig_start[a], bsig_start[z]), the transactions [tx_start[a], tx_start[z])
+ * and the parent hashes [hash_lo, hash_hi) (bv_plan_event_fields_shards); its
+ * items are its events followed by its ITXs.  Every non-empty shard takes the
+ * bulk pipeline on its slot, however small it is (an empty shard launches
+ * nothing).  It ships the creators' keys whole, then the distinct decoded keys
+ * of its own ITXs (the key cache is resolved per slot on those), its event
+ * range of every per-event array, its ITX range of itx_type, itx_str_off and
+ * the string bytes, its block-signature range of the bsig_* arrays and their
+ * bytes, its transaction slices, parent-hash range and signature text.  The
+ * slices keep the caller's values (nothing is rewritten on the host; arrays in
+ * bv_host_alloc memory cross by DMA from where they lie): the device subtracts
+ * the shard's bases.  Each slot's msg_hash, status, decided_by, itx_hash and
+ * itx_status land in the caller's buffers at its event / ITX bounds, copied by
+ * the host out of the slot's pinned result block as the single-context entries
+ * copy theirs (not by DMA into pinned caller buffers); only the accept
+ * bitmasks go through the gather of bv_group_verify_batch.
+ * A batch WITH in-batch parents (a SyncResponse DAG), or one the
+ * single-context entry runs on its one-launch small path (its routing
+ * decision, for the whole batch), is not sharded: it runs as one
+ * single-context call on device slot 0.
+ * After a failed call nothing stays in flight on any slot. */
+int bv_group_verify_events_itx(bv_group *g, const bv_event_itx_batch *batch, bv_result *result,
+                               bv_event_itx_out *out /* may be NULL */);
+int bv_group_verify_events_fields(bv_group *g, const bv_event_fields_batch *batch, bv_result *result,
+                                  bv_event_itx_out *out /* may be NULL */);
+/* Host helper (no device): the plan the two entries above follow.
+ * event_bounds, hash_lo, hash_hi and the return value (1: a batch with
+ * in-batch parents, whole on shard 0) are bv_plan_event_shards'; itx_bounds[d]
+ * = ev.itx_start[event_bounds[d]] (all 0 when ev.itx_start is NULL) and
+ * bsig_bounds[d] = bsig_start[event_bounds[d]], n_shards + 1 entries each.
+ * Reads only n_events, parent_kind, parent_ref, n_parent_hashes and those two
+ * start arrays at the bounds.  BV_E_ARGS on NULL pointers (bsig_start may be
+ * NULL only with n_events == 0), n_shards <= 0 and everything
+ * bv_plan_event_shards rejects. */
+int bv_plan_event_fields_shards(const bv_event_fields_batch *batch, int n_shards, uint64_t *event_bounds,
+                                uint64_t *itx_bounds, uint64_t *bsig_bounds, uint64_t *hash_lo, uint64_t *hash_hi);
 
 /* Blocks from their fields: Block.Verify (src/hashgraph/block.go:343-357),
  * CheckBlock (hashgraph.go:1599-1630), ProcessSigPool and the fast-forward

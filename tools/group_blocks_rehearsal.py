@@ -102,8 +102,7 @@ class OtherLib:
         rc = L.bv_create(ctypes.byref(self.ctx), 0, 0)
         if rc != native.BV_OK:
             raise native.BvError(rc, "bv_create (other library)")
-        self.arena = PinnedArena()
-        self.arena._L = L
+        self.arena = PinnedArena(lib=L)
 
     def call(self, cb, r, vc):
         return self._L.bv_verify_blocks(self.ctx, ctypes.byref(cb), ctypes.byref(r), vc)

@@ -55,8 +55,7 @@ class OtherLib:
         rc = L.bv_create(ctypes.byref(self.ctx), 0, 0)
         if rc != native.BV_OK:
             raise native.BvError(rc, "bv_create (other library)")
-        self.arena = PinnedArena()
-        self.arena._L = L
+        self.arena = PinnedArena(lib=L)
 
     def verify_events_into(self, eb, res):
         keep = []
